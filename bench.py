@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark: uint32 full sort, keys resident in HBM (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5] [--full] [--dump-outputs DIR]
+
+A plain run on one GPU sets up, warms up, times the K steps and prints the line
+(value, ms_per_step, the pass kernel's live roofline from the timed steps'
+events).  --full adds what takes steps or runs of its own: the per-kernel
+event steps, the verification, the CPU baseline, the host-ABI leg, the
+variants and the other configurations' legs (N > 1 always verifies and times
+its 8-bit variant: --full is implied there).  --dump-outputs DIR writes what the last timed
+step returned (float64 .npy: a fixed seeded sample and block sums of each
+output array); the inputs are the same stream in every run.
 
 c2 (default; the bench line): configs[1] = "256M uint32, 4-bit digits,
     gpuFullSort on 1 MI355X": 2^28 keys of the reference populateInput stream
@@ -94,6 +103,13 @@ def parse():
                     help="N>1: torch = one process per GPU (pylibsort.distrib over torch.distributed); cabi = rank "
                          "0 drives every GPU through the C ABI (libsortDistribSortU32 / ...PairsU64U32, the "
                          "single-process RCCL engine C and Go callers bind; gap-coded rounds at 2 GPUs); auto = cabi")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the per-kernel "
+                         "event steps, the verification, the CPU baseline, the host-ABI leg, the variants and the "
+                         "configs[2] / configs[4] / gpuPartial legs (each can be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; a fixed, seeded "
+                         "sample of a large output and the sum of every block of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-log2", type=int, default=28,
                     help="keys of the providedCpu baseline sample (BASELINE.md section 3: 2^28)")
@@ -364,35 +380,49 @@ def main():
                 got[name] = {"launches": launches, "avg_us": 1e3 * ms / launches, "keys_per_launch": kk / launches}
         return got
 
-    stage(rank, world, "timed steps done: %.3f s; per-kernel event steps" % elapsed)
+    stage(rank, world, "timed steps done: %.3f s" % elapsed)
     timed_pass = query(PASS_KERNELS.split(","))
-    D.timing_reset()
-    D.timing_sample(1)
-    D.timing_filter(None)
-    D.timing_enable(events)
-    for _ in range(2):
-        res = step()
-    torch.cuda.synchronize()
-    barrier()
-    D.timing_enable(False)
-    kern = query(("whist", "onesweep", "upsweep", "scan", "downsweep", "tilecounts", "colscan", "tilepass",
-                  "hybplan", "bucketsort", "partition", "histogram", "segcopy", "rsvsample"))
-    for name in kern:
-        kern[name]["from"] = "2 steps after the timed region"
+    if args.dump_outputs:
+        # what the last timed step returned (before any further step runs)
+        stage(rank, world, "writing the last timed step's outputs")
+        dump_outputs(torch, args.dump_outputs, res, pairs, rank, world)
+        barrier()
+    # everything below that takes steps or runs of its own is --full's: a
+    # plain one-GPU run goes from the timed steps to the line.  (N > 1 always
+    # takes them: the distributed result is checked in every run, and every
+    # rank has to take the same steps)
+    full = args.full or world > 1
+    kern = {}
+    if full:
+        stage(rank, world, "per-kernel event steps")
+        D.timing_reset()
+        D.timing_sample(1)
+        D.timing_filter(None)
+        D.timing_enable(events)
+        for _ in range(2):
+            res = step()
+        torch.cuda.synchronize()
+        barrier()
+        D.timing_enable(False)
+        kern = query(("whist", "onesweep", "upsweep", "scan", "downsweep", "tilecounts", "colscan", "tilepass",
+                      "hybplan", "bucketsort", "partition", "histogram", "segcopy", "rsvsample"))
+        for name in kern:
+            kern[name]["from"] = "2 steps after the timed region"
     kern.update({name: dict(v, **{"from": "the timed steps"}) for name, v in timed_pass.items()})
 
     # verification outside the timed region: sorted + same multiset (checksums)
-    stage(rank, world, "verification")
     verified = None
-    if not args.no_verify and cabi:
-        verified = verify_cabi(torch, shards, res, vshards if pairs else None) if rank == 0 else None
-    elif not args.no_verify:
-        verified = verify(torch, dist, world, keys, res, vals)
+    if full and not args.no_verify:
+        stage(rank, world, "verification")
+        if cabi:
+            verified = verify_cabi(torch, shards, res, vshards if pairs else None) if rank == 0 else None
+        else:
+            verified = verify(torch, dist, world, keys, res, vals)
 
     # N>1: the same distributed sort with 8-bit local digits (all ranks take
     # part; max over ranks), reported beside the 4-bit line, never as `value`
     variant8 = None
-    if world > 1 and not args.no_variants and not pairs:
+    if full and world > 1 and not args.no_variants and not pairs:
         stage(rank, world, "8-bit digit variant")
         prev = pylibsort.setDigitBits(8)
         for _ in range(2):
@@ -438,7 +468,7 @@ def main():
             # kernel trace, so `frac` can be re-derived from profiles/
             if args.workload == "c2" and world == 1 and args.keys_log2 == 28 and ds_name == "tilepass":
                 roofline.update(committed_profile(bytes_per_launch))
-        if roofline is not None and world == 1 and not pairs:
+        if full and roofline is not None and world == 1 and not pairs:
             roofline["step"] = step_roofline(n, args.digit_bits, ms_per_step, kern)
         bs = kern.get("bucketsort")
         if bs:
@@ -448,12 +478,12 @@ def main():
                 bs["frac"] = round(ach / HBM_PEAK_GBPS, 4)
                 bs["bytes_per_key"] = 8.0
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and not pairs:
+        if full and world == 1 and not args.no_cpu_baseline and not pairs:
             cpu = cpu_baseline_leg(torch, pylibsort, keys, out, args.cpu_sample_log2)
         variants = {}
         if world > 1 and variant8 is not None:
             variants["digit8"] = variant8
-        if world == 1 and not args.no_variants and args.workload == "c2":
+        if full and world == 1 and not args.no_variants and args.workload == "c2":
             ref_out = out.clone()
             prev = pylibsort.setDigitBits(8)
             settle(lambda: D.sort_keys_u32(keys, out=out, tmp=tmp), torch)
@@ -470,19 +500,21 @@ def main():
             variants["digit8"] = {"ms_per_step": round(ms8, 4), "value": round(n / (ms8 * 1e-3) / 1e9, 3),
                                   "note": "same sort with 8-bit digits (4 passes, configs[2] digit width); output "
                                           "checked equal to the 4-bit sort"}
-        if world == 1 and not args.no_variants and args.workload == "c2":
+        if full and world == 1 and not args.no_variants and args.workload == "c2":
             variants["lsd"] = lsd_variant(torch, pylibsort, D, keys, out, tmp, max(5, args.steps // 2))
             variants["bucket_lsd_steps"] = bucket_steps_variant(torch, pylibsort, D, keys, out, tmp,
                                                                 max(5, args.steps // 2))
-        if world == 1 and not args.no_variants and not args.no_legs and args.workload == "c2" and args.keys_log2 == 28:
+        legs = full and world == 1 and not args.no_variants and not args.no_legs and args.workload == "c2" and \
+            args.keys_log2 == 28
+        if legs:
             # the other single-GPU configurations, each with its own live
             # per-kernel timings (never `value`)
             variants["c3"] = config_leg(torch, pylibsort, D, "c3", max(5, args.steps // 2))
             variants["c5"] = config_leg(torch, pylibsort, D, "c5", max(5, args.steps // 2))
         host_abi = None
-        if world == 1 and not args.no_host_abi and args.workload == "c2":
+        if full and world == 1 and not args.no_host_abi and args.workload == "c2":
             host_abi = host_abi_leg(torch, pylibsort, keys, out)
-        if world == 1 and not args.no_variants and not args.no_legs and args.workload == "c2" and args.keys_log2 == 28:
+        if legs:
             # gpuPartial at the reference's own benchmark workload (these
             # overwrite `out`: after every use of the line's sorted keys)
             for w in (8, 16):
@@ -528,6 +560,7 @@ def main():
                        "note": "untimed steps before the W warm-up steps (N=1): the GPU's clocks settle over the "
                                "first ~30 ms of sorting after idling (profiles/r06i_clock_settle.txt)"},
             "ms_per_step": round(ms_per_step, 4),
+            "full": full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -564,6 +597,65 @@ def main():
     if world > 1:
         dist.barrier(group=cpu_pg)
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 21  # --dump-outputs: elements sampled of each output array (over all shards)
+DUMP_BLOCK = 8192      # --dump-outputs: every array's block sums cover all of it (exact in float64: < 2^45)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(torch, directory, res, pairs, rank, world):
+    """--dump-outputs DIR: what the last timed step returned, as float64
+    DIR/<name>.npy.  Per output array (the sorted uint32 keys; pairs: the high
+    and low words of the sorted u64 keys and the payloads) a sample at fixed
+    positions (seeded; the whole array when it is no longer than the sample)
+    and the sums of its consecutive DUMP_BLOCK-element blocks, so every
+    element bears on the dump: at most 64 MB in all.  N > 1: one set per
+    shard (`_shard<r>`), written by the process that holds it."""
+    import numpy as np
+    if res is None:  # (a rank that only keeps the barriers while rank 0 drives the C engine)
+        return
+    ks, vs = res if pairs else (res, None)
+    if isinstance(ks, (list, tuple)):  # the C engine at N > 1: every shard on rank 0
+        shards = [("_shard%d" % r, k, vs[r] if pairs else None) for r, k in enumerate(ks)]
+    else:
+        shards = [("" if world == 1 else "_shard%d" % rank, ks, vs)]
+    out_dir = pathlib.Path(directory)
+    out_dir.mkdir(parents=True, exist_ok=True)
+
+    def u32(t):
+        return t.to(torch.int64) & 0xFFFFFFFF
+
+    def words(k, v):
+        """(name, tensor -> its values as non-negative int64, tensor) per array"""
+        if v is None:
+            return [("sorted_keys", u32, k)]
+        return [("sorted_keys_hi", lambda t: (t >> 32) & 0xFFFFFFFF, k), ("sorted_keys_lo", u32, k),
+                ("sorted_vals", u32, v)]
+
+    for suffix, k, v in shards:
+        n = k.numel()
+        m = max(1, DUMP_SAMPLE // world)
+        idx = None
+        if n > m:
+            pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, m, dtype=np.int64))
+            idx = torch.from_numpy(pos).to(k.device)
+        for name, conv, t in words(k, v):
+            t = t.reshape(-1)
+            sample = conv(t if idx is None else t[idx]).to(torch.float64)
+            np.save(out_dir / ("%s%s.npy" % (name, suffix)), sample.cpu().numpy())
+            sums = []
+            chunk = DUMP_BLOCK << 12  # (converted 2^25 elements at a time)
+            for lo in range(0, n, chunk):
+                c = conv(t[lo:lo + chunk])
+                whole = c.numel() // DUMP_BLOCK * DUMP_BLOCK
+                if whole:
+                    sums.append(c[:whole].view(-1, DUMP_BLOCK).sum(1))
+                if whole < c.numel():  # (the array's short last block)
+                    sums.append(c[whole:].sum().reshape(1))
+            if sums:
+                np.save(out_dir / ("%s_block_sums%s.npy" % (name, suffix)),
+                        torch.cat(sums).to(torch.float64).cpu().numpy())
 
 
 PROFILE_TAG = "r06y"  # profiles/<tag>_* of this round's build (tools/collect_profiles.sh)

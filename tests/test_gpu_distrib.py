@@ -262,7 +262,7 @@ def test_bench_single_gpu_line_contract():
     import subprocess
     import sys
     root = pathlib.Path(__file__).resolve().parents[1]
-    cmd = [sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "1", "--keys-log2", "24",
+    cmd = [sys.executable, str(root / "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--keys-log2", "24",
            "--cpu-sample-log2", "18"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=180, cwd=str(root))
     assert r.returncode == 0, r.stderr[-4000:]
@@ -280,3 +280,44 @@ def test_bench_single_gpu_line_contract():
     assert d["cpu_baseline"]["nproc"] >= 1 and d["cpu_baseline"]["host_cpu"]
     assert d["host_abi"]["value"] > 0 and d["variants"]["digit8"]["value"] > 0
     assert d["settle"]["steps"] >= 2 and d["settle"]["seconds"] > 0  # untimed clock-settle steps, reported
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` goes from the timed
+    steps to the line: no per-kernel steps, verification, CPU baseline,
+    variants or legs (those are --full's).  --dump-outputs writes what the
+    last timed step returned: here 2^22 keys (twice the sample), checked
+    against the oracle's sort of the same stream -- the sample at the seeded
+    positions, and the block sums over every key."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import json
+    import pathlib
+    import subprocess
+    import sys
+    import bench
+    from oracle import oracle
+    root = pathlib.Path(__file__).resolve().parents[1]
+    n = 1 << 22
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--keys-log2", "22",
+           "--dump-outputs", str(tmp_path / "dump")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=180, cwd=str(root))
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["metric"] == "Gkeys/sec uint32 full sort" and d["unit"] == "Gkeys/s" and d["dtype"] == "u32"
+    assert d["higher_is_better"] is True and d["ms_per_step"] > 0
+    # value = keys / step time (the line rounds ms_per_step to 4 places, value to 3)
+    assert abs(d["value"] - n / (d["ms_per_step"] * 1e-3) / 1e9) <= d["value"] * 1e-4 / d["ms_per_step"] + 1e-3
+    assert d["verified"] is None and d["cpu_baseline"] is None and d["variants"] is None and d["host_abi"] is None
+    assert set(d["kernels"]) <= set(bench.PASS_KERNELS.split(","))  # only the timed steps' own events
+    want = oracle.sort_u32(oracle.pcg(n)).astype(np.float64)
+    got = np.load(tmp_path / "dump" / "sorted_keys.npy")
+    sums = np.load(tmp_path / "dump" / "sorted_keys_block_sums.npy")
+    assert got.dtype == np.float64 and sums.dtype == np.float64
+    pos = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n, bench.DUMP_SAMPLE, dtype=np.int64))
+    np.testing.assert_array_equal(got, want[pos])
+    np.testing.assert_array_equal(sums, want.reshape(-1, bench.DUMP_BLOCK).sum(1))
+    assert sorted(p.name for p in (tmp_path / "dump").iterdir()) == ["sorted_keys.npy", "sorted_keys_block_sums.npy"]

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 for r in $(seq 1 "$ROUNDS"); do
   for wl in "$@"; do
     for v in $VALS; do
-      env "$VAR=$v" timeout -k 10 200 python3 bench.py --workload "$wl" --steps 10 --warmup 3 --no-cpu-baseline \
+      env "$VAR=$v" timeout -k 10 200 python3 bench.py --full --workload "$wl" --steps 10 --warmup 3 --no-cpu-baseline \
         --no-variants --no-host-abi --no-legs > "$OUT/${wl}_${v}_$r.json" 2> "$OUT/${wl}_${v}_$r.err" || { echo "bench $wl $v failed"; tail -5 "$OUT/${wl}_${v}_$r.err"; exit 1; }
       python3 - "$OUT/${wl}_${v}_$r.json" "$VAR=$v" "$wl" <<'PY'
 import json, sys

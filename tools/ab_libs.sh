@@ -3,16 +3,17 @@
 # variant) with the in-tree libsort.so and with each build_ab/*.so given.
 #   tools/ab_libs.sh build_ab/a.so build_ab/b.so ...
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out/ab
-rm -f gpurun_out/ab/*.json
+OUT=${BENCH_OUT:-bench_out}/ab
+mkdir -p "$OUT"
+rm -f "$OUT"/*.json
 for i in $(seq 1 ${AB_REPS:-2}); do
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-legs --no-host-abi $AB_ARGS > gpurun_out/ab/intree_$i.json 2>/dev/null || exit 1
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-legs --no-host-abi $AB_ARGS > "$OUT/intree_$i.json" 2>/dev/null || exit 1
   for lib in "$@"; do
-    LIBSORT_PATH=$PWD/$lib timeout -k 10 200 python bench.py --no-cpu-baseline --no-legs --no-host-abi $AB_ARGS \
-      > gpurun_out/ab/$(basename $lib .so)_$i.json 2>/dev/null || exit 1
+    LIBSORT_PATH=$PWD/$lib timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-legs --no-host-abi $AB_ARGS \
+      > "$OUT/$(basename $lib .so)_$i.json" 2>/dev/null || exit 1
   done
 done
-for f in gpurun_out/ab/*.json; do
+for f in "$OUT"/*.json; do
   python - "$f" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); k = d["kernels"]

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round measurement on the GPU box, all of the driver's EXACT bench command
-# (python3 bench.py --gpus 1 --steps 20 --warmup 5), in this order:
+# with every leg (python3 bench.py --gpus 1 --steps 20 --warmup 5 --full), in this order:
 #   1. FETCH_SIZE / WRITE_SIZE passes (separate runs, kernel trace only,
 #      restricted to the pass kernel) -> HBM bytes per launch;
 #   2. rocprofv3 --kernel-trace --stats -> per-dispatch durations;
@@ -14,7 +14,7 @@ TAG=${1:-r02}
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python3 bench.py --gpus 1 --steps 20 --warmup 5"
+BENCH="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full"
 echo "$BENCH" > "$OUT/cmd.txt"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c -d "$OUT/pmc_$c" -o run --output-format csv \

@@ -12,6 +12,6 @@ timeout -k 10 1000 python -u -m pytest -x -v --timeout 300 --timeout-method thre
 tail -3 "$OUT/pytest.log"
 timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { echo "smoke failed"; tail -20 "$OUT/smoke.log"; exit 1; }
 cat "$OUT/smoke.log"
-timeout -k 10 400 python3 bench.py > "$OUT/bench1.json" 2> "$OUT/bench1.err" || { echo "bench failed"; tail -20 "$OUT/bench1.err"; exit 1; }
+timeout -k 10 400 python3 bench.py --full > "$OUT/bench1.json" 2> "$OUT/bench1.err" || { echo "bench failed"; tail -20 "$OUT/bench1.err"; exit 1; }
 cat "$OUT/bench1.json"
 echo done
