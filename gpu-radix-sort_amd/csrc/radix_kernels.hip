@@ -1194,7 +1194,7 @@ struct HybridGeo {
 #define LIBSORT_HYB_ATOMIC_RANK 1
 #endif
 template <int BITS, int BLOCK, int ITEMS, typename K, typename V, bool FUSE, typename Op = RadixDigit,
-          typename OpN = RadixDigit, int GEO = 0, bool ANY_ORDER = false>
+          typename OpN = RadixDigit, int GEO = 0, bool ANY_ORDER = false, int P16 = 0>
 __global__ __launch_bounds__(BLOCK) LS_TP_ATTR void k_tile_pass(const K* __restrict__ kin, K* __restrict__ kout,
                                                      const V* __restrict__ vin, V* __restrict__ vout,
                                                      uint32_t n, Op op_in, OpN op_next,
@@ -1240,6 +1240,16 @@ __global__ __launch_bounds__(BLOCK) LS_TP_ATTR void k_tile_pass(const K* __restr
   // per digit on its range's slice cursor) instead of where a count pass and
   // a column scan put them; keys only (any order within a run).
   constexpr bool RSV = (GEO & 4) != 0;
+  // P16 (the last digit pass of a full-width keys-only hybrid sort, "pack16";
+  // DESIGN.md section 3): the pass's digit is the last of the key's top 16
+  // bits, which the bucket index restates, so only (uint16_t)key is written,
+  // to geo.o16 at the key's element index (nothing to kout).  1: one 2-byte
+  // store per key; 2 (A/B builds only, LIBSORT_PACK16_PAIRED_AB; measured
+  // slower): full tiles write two neighbours of a run
+  // that share a global dword as one dword store (2-byte stores at run heads
+  // and tails).
+  static_assert(P16 == 0 || (GEO == 1 && !FUSE && ANY_ORDER && sizeof(K) == 4 && !HAS_V && ITEMS % (2 * SPLIT) == 0),
+                "pack16: the keys-only last pass over a tile table");
   static_assert(!RSV || (ANY_ORDER && !HAS_V && (GEO & 2) == 0), "reserved placement: keys-only depth 0");
   __shared__ uint32_t s_over;
 
@@ -1512,7 +1522,62 @@ __global__ __launch_bounds__(BLOCK) LS_TP_ATTR void k_tile_pass(const K* __restr
     return;
   }
 
-  if (full) {
+  if constexpr (P16 != 0) {
+    uint16_t* const o16 = geo.o16;
+    if (P16 == 2 && full) {
+      // thread m owns local positions a = 2m, b = 2m + 1 and reads their
+      // neighbours p = 2m - 1, x = 2m + 2.  A key at an even global index
+      // takes its successor along in one dword when both are of one run; a key
+      // at an odd global index is written by its predecessor's thread, or
+      // alone when it heads its run.  A dword never leaves the tile's run:
+      // neighbouring tiles and buckets share dwords.
+      constexpr int PAIRS = TILE / 2, PJ = (PAIRS + BLOCK - 1) / BLOCK;
+#pragma unroll
+      for (int j = 0; j < PJ; ++j) {
+        const uint32_t m = tid + j * BLOCK;
+        if (PAIRS % BLOCK == 0 || m < (uint32_t)PAIRS) {
+          const uint2 ab = make_uint2((uint32_t)s_keys[2 * m], (uint32_t)s_keys[2 * m + 1]);
+          const uint32_t da = op((K)ab.x), db = op((K)ab.y);
+          const uint32_t dp = m > 0 ? op(s_keys[2 * m - 1]) : (uint32_t)RADIX;
+          const K kx = 2 * m + 2 < (uint32_t)TILE ? s_keys[2 * m + 2] : (K)0;
+          const uint32_t dx = 2 * m + 2 < (uint32_t)TILE ? op(kx) : (uint32_t)RADIX;
+          const uint32_t ga = ob_base(s_ob[da]) + 2 * m, gb = ob_base(s_ob[db]) + 2 * m + 1;
+          if ((ga & 1u) == 0) {
+            if (da == db)
+              *reinterpret_cast<uint32_t*>(o16 + ga) = (ab.x & 0xFFFFu) | (ab.y << 16);
+            else
+              o16[ga] = (uint16_t)ab.x;
+          } else if (dp != da) {
+            o16[ga] = (uint16_t)ab.x;
+          }
+          if (gb & 1u) {
+            if (da != db) o16[gb] = (uint16_t)ab.y;
+          } else if (dx == db) {
+            *reinterpret_cast<uint32_t*>(o16 + gb) = (ab.y & 0xFFFFu) | ((uint32_t)kx << 16);
+          } else {
+            o16[gb] = (uint16_t)ab.y;
+          }
+        }
+      }
+    } else if (full) {
+#pragma unroll
+      for (int h = 0; h < SPLIT; ++h) {
+        K kk[SP];
+        OB ob[SP];
+#pragma unroll
+        for (int j = 0; j < SP; ++j) kk[j] = s_keys[tid + (h * SP + j) * BLOCK];
+#pragma unroll
+        for (int j = 0; j < SP; ++j) ob[j] = s_ob[op(kk[j])];
+#pragma unroll
+        for (int j = 0; j < SP; ++j) o16[ob_base(ob[j]) + tid + (h * SP + j) * BLOCK] = (uint16_t)kk[j];
+      }
+    } else {
+      for (uint32_t i = tid; i < valid; i += BLOCK) {
+        const K kk = s_keys[i];
+        o16[ob_base(s_ob[op(kk)]) + i] = (uint16_t)kk;
+      }
+    }
+  } else if (full) {
     // unrolled halves: the LDS reads of a half issue back to back, then its
     // global stores, then (FUSE) its next-digit LDS atomics
 #pragma unroll
@@ -1695,10 +1760,9 @@ constexpr uint32_t kRetryMax = 16;
 // keys: the caller lists the bucket for the LSD steps).  Replaces round 4's
 // separate 3-bit LIST launch over those buckets (~45 us per 2^28 sort: two
 // latency-bound rounds of ~20 us buckets).
-template <int BLOCK, int ITEMS, typename ValFn>
+template <int BLOCK, int ITEMS, typename ValFn, typename ValidFn>
 __device__ __forceinline__ bool retry3_halves(const uint32_t (&k)[ITEMS], uint32_t (&rk)[ITEMS], uint32_t* s_mem,
-                                              uint32_t* s_wsum, uint32_t len, uint32_t wbase, uint32_t lane,
-                                              ValFn val) {
+                                              uint32_t* s_wsum, uint32_t lane, ValFn val, ValidFn valid) {
   constexpr uint32_t HC = kCntCells / 2, PER2 = HC / BLOCK;
   static_assert(PER2 >= 1 && HC % BLOCK == 0, "half-cells per thread");
   uint64_t* const s_c = reinterpret_cast<uint64_t*>(s_mem);
@@ -1714,7 +1778,7 @@ __device__ __forceinline__ bool retry3_halves(const uint32_t (&k)[ITEMS], uint32
     bool ovf = false;
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j)
-      if (wbase + j * kWave + lane < len) {
+      if (valid(j)) {
         const uint32_t v = val(k[j]), c = v >> 4;
         if ((c / HC) == h) {
           const uint32_t sh = 3u * (v & 15u);
@@ -1743,7 +1807,7 @@ __device__ __forceinline__ bool retry3_halves(const uint32_t (&k)[ITEMS], uint32
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j)
-      if (wbase + j * kWave + lane < len) {
+      if (valid(j)) {
         const uint32_t v = val(k[j]), c = v >> 4;
         if ((c / HC) == h) {
           const uint64_t cc = s_c[ci2(c % HC)];
@@ -1763,7 +1827,10 @@ __device__ __forceinline__ bool retry3_halves(const uint32_t (&k)[ITEMS], uint32
 // overflow's weight: kCnt2F the threads that saw a count wrap (a uniform
 // bucket's overflow is one value with 4 keys: 1-2; a duplicate-heavy bucket
 // wraps in most threads), the other modes 1.
-template <int BLOCK, int ITEMS, int MODE, typename Op, bool INL = false>
+// P16 (pack16 input, k_bucket_count): item j = 2q + h is half h of the q-th
+// dword the thread loaded, slot 2 * (w * (ITEMS / 2) * 64 + q * 64 + lane) + h
+// counted from the bucket's dword-aligned floor, start & 1 slots below start.
+template <int BLOCK, int ITEMS, int MODE, typename Op, bool INL = false, bool P16 = false>
 __device__ __forceinline__ uint32_t bucket_count_place(const uint32_t (&k)[ITEMS], uint64_t* s_cw, uint32_t* out,
                                                    uint32_t start, uint32_t len, uint32_t lbits_in, uint32_t bias) {
   constexpr int PER = kCntCells / BLOCK;
@@ -1780,7 +1847,12 @@ __device__ __forceinline__ uint32_t bucket_count_place(const uint32_t (&k)[ITEMS
   auto ci = [&](uint32_t c) -> uint32_t { return (c % PER) * BLOCK + c / PER; };
   auto val = [&](uint32_t x) -> uint32_t { return (BIAS ? x - bias : x) & lmask; };
   uint32_t* const s_keys = reinterpret_cast<uint32_t*>(s_cw);
-  auto valid = [&](int j) { return wbase + j * kWave + lane < len; };
+  auto valid = [&](int j) {
+    if constexpr (P16)
+      return wbase + (uint32_t)(j >> 1) * (2 * kWave) + 2u * lane + (uint32_t)(j & 1) - (start & 1u) < len;
+    else
+      return wbase + j * kWave + lane < len;
+  };
 
   uint32_t rk[ITEMS];
   uint32_t rkp[(ITEMS + 1) / 2];  // kCntSmall: packed 16-bit ranks / positions
@@ -1809,7 +1881,7 @@ __device__ __forceinline__ uint32_t bucket_count_place(const uint32_t (&k)[ITEMS
       // light (a few values with 4+ keys): the 3-bit retry inline (INL);
       // heavy, or a 3-bit wrap: the caller lists the bucket
       if (!INL || sev > kRetryMax) return sev;
-      if (!retry3_halves<BLOCK, ITEMS>(k, rk, s_keys, s_ws2, len, wbase, lane, val)) return kRetryMax + 1;
+      if (!retry3_halves<BLOCK, ITEMS>(k, rk, s_keys, s_ws2, lane, val, valid)) return kRetryMax + 1;
     } else {
       uint32_t cnt[PER], sum = 0;
 #pragma unroll
@@ -1944,7 +2016,14 @@ __device__ __forceinline__ uint32_t bucket_count_place(const uint32_t (&k)[ITEMS
 // written nothing and listed: in retry_list when given and its overflow
 // weighs <= kRetryMax (a few values with 4+ keys), else in ovf_list (the LSD
 // steps of k_bucket_sort LIST), so this kernel holds no LSD-step code.
-template <int BLOCK, int ITEMS, typename Op, int MODE, bool LIST = false, bool INL = false>
+// P16 (pack16): `in` is the u16 array the last digit
+// pass wrote (element i = the low 16 bits of out's element i, the base 4-byte
+// aligned), and bucket b's keys are (b << 16) | element.  The bucket's range
+// [start, start + len) is read with dword loads from its aligned floor, two
+// elements per lane per load, the elements outside the bucket masked (an odd
+// start takes one slot more than len: the block has 2 * ceil(ITEMS / 2) slots
+// per thread).  in != out, so an overflowed bucket's input stays as it was.
+template <int BLOCK, int ITEMS, typename Op, int MODE, bool LIST = false, bool INL = false, bool P16 = false>
 __global__ __launch_bounds__(BLOCK)
 __attribute__((amdgpu_waves_per_eu(
     BLOCK >= 1024 && ITEMS <= 17 && MODE != kCntSmall ? 8 : (BLOCK == 256 && ITEMS <= 17 && MODE == kCntSmall) ? 7 : 1,
@@ -1961,7 +2040,8 @@ void k_bucket_count(const uint32_t* in, uint32_t* out, const uint32_t* __restric
   const uint32_t wbase = (threadIdx.x / kWave) * ITEMS * kWave, lane = threadIdx.x & (kWave - 1);
   auto one = [&](const uint32_t b) {
     const uint32_t start = bstart[b], len = blen[b];
-    if (len > (uint32_t)CAP) {
+    // (P16, an even ITEMS: an odd start leaves CAP - 1 slots)
+    if (len > (uint32_t)CAP || (P16 && ITEMS % 2 == 0 && len + (start & 1u) > (uint32_t)CAP)) {
       if (threadIdx.x == 0) {
         const uint32_t slot = atomicAdd(oversized, 1u);
         if (olist && slot < olist_cap) olist[slot] = b;
@@ -1969,13 +2049,30 @@ void k_bucket_count(const uint32_t* in, uint32_t* out, const uint32_t* __restric
       return;
     }
     if (len == 0) return;
-    uint32_t k[ITEMS];
+    uint32_t sev;
+    if constexpr (P16) {
+      constexpr int ND = (ITEMS + 1) / 2;
+      const uint32_t par = start & 1u, nd = (par + len + 1u) >> 1;
+      const uint32_t* const in32 = in + (start >> 1);
+      const uint32_t dbase = (threadIdx.x / kWave) * ND * kWave + lane, hb = b << 16;
+      uint32_t k[2 * ND];
 #pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-      const uint32_t i = wbase + j * kWave + lane;
-      k[j] = i < len ? load_stream(&in[(size_t)start + i]) : 0u;
+      for (int q = 0; q < ND; ++q) {
+        const uint32_t i = dbase + q * kWave;
+        const uint32_t x = i < nd ? load_stream(&in32[i]) : 0u;
+        k[2 * q] = hb | (x & 0xFFFFu);
+        k[2 * q + 1] = hb | (x >> 16);
+      }
+      sev = bucket_count_place<BLOCK, 2 * ND, MODE, Op, INL, true>(k, s_cw, out, start, len, lbits, bias);
+    } else {
+      uint32_t k[ITEMS];
+#pragma unroll
+      for (int j = 0; j < ITEMS; ++j) {
+        const uint32_t i = wbase + j * kWave + lane;
+        k[j] = i < len ? load_stream(&in[(size_t)start + i]) : 0u;
+      }
+      sev = bucket_count_place<BLOCK, ITEMS, MODE, Op, INL>(k, s_cw, out, start, len, lbits, bias);
     }
-    const uint32_t sev = bucket_count_place<BLOCK, ITEMS, MODE, Op, INL>(k, s_cw, out, start, len, lbits, bias);
     if (sev && threadIdx.x == 0) {  // (in == out keeps the bucket for the next try)
       if (!INL && retry_list && sev <= kRetryMax)
         retry_list[atomicAdd(retry_n, 1u)] = b;
@@ -2158,8 +2255,11 @@ __global__ __launch_bounds__(BLOCK) void k_bucket_pairs(const uint64_t* kin, uin
 // LIST: a persistent grid walks a list of buckets (ilist[0, min(*nb,
 // nb_cap))) -- the launch after the counting placement, over its overflow
 // list.
+// P16 (that list after a pack16 last pass): `in` is the u16 array, bucket b's
+// keys (b << 16) | element (2-byte loads: the list is short, or the buckets
+// duplicate-heavy and bound by their LSD steps).
 template <int BITS, int BLOCK, int ITEMS, typename Op = RadixDigit, typename K = uint32_t, typename V = NoValue,
-          int FIX = 0, bool LIST = false>
+          int FIX = 0, bool LIST = false, bool P16 = false>
 __global__ __launch_bounds__(BLOCK) void k_bucket_sort(const K* in, K* out, const V* vin, V* vout,
                                                        const uint32_t* __restrict__ bstart,
                                                        const uint32_t* __restrict__ blen,
@@ -2208,7 +2308,10 @@ __global__ __launch_bounds__(BLOCK) void k_bucket_sort(const K* in, K* out, cons
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
       const uint32_t i = wbase + j * kWave + lane;
-      k[j] = i < len ? load_stream(&in[(size_t)start + i]) : pad;
+      if constexpr (P16)
+        k[j] = i < len ? (K)((b << 16) | reinterpret_cast<const uint16_t*>(in)[(size_t)start + i]) : pad;
+      else
+        k[j] = i < len ? load_stream(&in[(size_t)start + i]) : pad;
       if constexpr (HAS_V) v[j] = i < len ? load_stream(&vin[(size_t)start + i]) : (VS)0;
     }
   };
@@ -2405,6 +2508,20 @@ __global__ __launch_bounds__(BLOCK) void k_bucket_sort(const K* in, K* out, cons
   } else {
     if (blockIdx.x >= min(*nb, nb_cap)) return;
     one(ilist ? ilist[blockIdx.x] : blockIdx.x);
+  }
+}
+
+// pack16's way back to whole keys, before the host-level LSD fallback sorts
+// out in place: out[i] = (b << 16) | in16[i] for every element i of every
+// bucket b.  Blocks stride over the buckets (x) and, within one, over its
+// elements (y): a bucket may hold any number of keys here.
+__global__ __launch_bounds__(256) void k_pack16_expand(const uint16_t* __restrict__ in16, uint32_t* __restrict__ out,
+                                                       const uint32_t* __restrict__ bstart,
+                                                       const uint32_t* __restrict__ blen, uint32_t nb) {
+  for (uint32_t b = blockIdx.x; b < nb; b += gridDim.x) {
+    const uint32_t start = bstart[b], len = blen[b], hb = b << 16;
+    for (uint32_t i = blockIdx.y * 256u + threadIdx.x; i < len; i += gridDim.y * 256u)
+      out[(size_t)start + i] = hb | in16[(size_t)start + i];
   }
 }
 
@@ -4080,6 +4197,23 @@ inline int rsv_mode() {
   return s[0] == '0' ? 0 : s[0] == 's' ? 2 : s[0] == 'n' ? 3 : 1;
 }
 
+// pack16 (sort_hybrid): the last digit pass of a full-width keys-only sort
+// writes 16-bit keys and the bucket kernels read them.  LIBSORT_HYB_PACK16=0
+// keeps whole keys; anything else, or unset: on.  Read per call (the tests
+// switch it in process).  An A/B build (-DLIBSORT_PACK16_PAIRED_AB=1) also
+// holds the last pass's paired dword stores, picked by =b (2-byte stores: =a):
+// 2.04-2.06 against 2.03-2.04 ms per 2^28-key sort, 1.56 against 1.50 ms at
+// 8-bit digits, 3 interleaved runs each (profiles/pack16_ab.txt), so the
+// product build does not instantiate it.
+#ifndef LIBSORT_PACK16_PAIRED_AB
+#define LIBSORT_PACK16_PAIRED_AB 0
+#endif
+inline int pack16_mode() {
+  const char* s = getenv("LIBSORT_HYB_PACK16");
+  if (!s) return 1;
+  return s[0] == '0' ? 0 : (LIBSORT_PACK16_PAIRED_AB && s[0] == 'b') ? 2 : 1;
+}
+
 // The 2-bit counting cells for 256-thread bucket blocks (kCnt2F);
 // LIBSORT_BUCKET2=0 keeps the 3-bit cells (A/B).
 inline bool bucket2_on() {
@@ -4596,6 +4730,20 @@ hipError_t sort_hybrid(Workspace& ws, const K* in, K* out, K* tmp, const V* vin,
     rmode = 0;
   }
   const bool rsv = rmode != 0;
+  // pack16: after the last digit pass of a full-width
+  // sort every key sits in the bucket of its top 16 bits and the bucket index
+  // is that prefix, so the last pass writes only the low 16 bits (2 B per key
+  // instead of 4) and the bucket kernels read them back (2 instead of 4): 36
+  // instead of 40 B per key and sort.  The u16 array (element i = out's
+  // element i) goes to a buffer that is neither the last pass's source nor
+  // out: the slices of the reserved depth 0, which depth 1 has consumed (n / 2
+  // words, below the cursors), or tmp when the last pass reads the slices (two
+  // depths).  Needs the counting placement and the reserved depth 0 (not its
+  // test mode with short slices, whose overflow abandons the later depths).
+  constexpr bool kP16Ok = kCntOk && std::is_same<Op, RadixDigit>::value;
+  const int p16 = (kP16Ok && !pc && W == 32 && lbits == 16 && cnt && rmode == 1) ? pack16_mode() : 0;
+  uint16_t* const p16buf =
+      !p16 ? nullptr : DEPTHS >= 3 ? reinterpret_cast<uint16_t*>(ws.rsv) : reinterpret_cast<uint16_t*>(tmp);
   // 24-bit pieces are read by the reserved depth 0 only: otherwise the
   // caller's gather (which unpacks them) and LSD sort
   if (pc && pc->i8 && !rsv) return hipSuccess;
@@ -4794,9 +4942,25 @@ hipError_t sort_hybrid(Workspace& ws, const K* in, K* out, K* tmp, const V* vin,
     }
     HybridGeo geo{tiles[k & 1], ctr + k, cstart[(k + 1) & 1], ctile0[(k + 1) & 1], nullptr, nullptr, nullptr, nullptr, 0u};
     if (BITS == 8 && dstream && !last) geo.dout = ws.dstream;  // the next depth's digits
+    if (last && p16) {
+      // (the registry's sign that the packed last pass ran; no launch)
+      ScopedTimer mark("pack16", st, n);
+    }
     {
       ScopedTimer tm("tilepass", st, n);
-      if (BITS == 4 && !last) {
+      if (last && p16) {
+        if constexpr (kP16Ok) {
+          geo.o16 = p16buf;
+#if LIBSORT_PACK16_PAIRED_AB
+          if (p16 == 2)
+            hipLaunchKernelGGL((k_tile_pass<BITS, B, ITEMS, K, V, false, Op, Op, 1, true, 2>), dim3(rows), dim3(B), 0,
+                               st, src, dst, vsrc, vdst, (uint32_t)n, op, op_next, C, ws.tb, segbase, Cn, geo);
+          else
+#endif
+            hipLaunchKernelGGL((k_tile_pass<BITS, B, ITEMS, K, V, false, Op, Op, 1, true, 1>), dim3(rows), dim3(B), 0,
+                               st, src, dst, vsrc, vdst, (uint32_t)n, op, op_next, C, ws.tb, segbase, Cn, geo);
+        }
+      } else if (BITS == 4 && !last) {
         if (!tab)
           hipLaunchKernelGGL((k_tile_pass<BITS, B0, ITEMS, K, V, BITS == 4, Op, Op, 2, kAnyOrder>),
                              dim3(rows), dim3(B0), 0, st, src, dst, vsrc, vdst, (uint32_t)n, op, op_next, C,
@@ -4848,6 +5012,13 @@ hipError_t sort_hybrid(Workspace& ws, const K* in, K* out, K* tmp, const V* vin,
   if (rsv && ws.hyb_host[259]) return hipSuccess;
   *handled = true;
   if (ws.hyb_host[257] > kListCap || ws.hyb_host[256] > cap) {
+    if (p16) {
+      // (the packed last pass is already queued: whole keys into out first)
+      ScopedTimer tm("pack16expand", st, n);
+      hipLaunchKernelGGL(k_pack16_expand, dim3(std::min<uint32_t>(NB, 4096u), 8), dim3(256), 0, st, p16buf,
+                         reinterpret_cast<uint32_t*>(out), cstart[DEPTHS & 1], nsize, NB);
+      LS_TRY(hipGetLastError());
+    }
     // pieces: every bit (the segments' own bits vary across out)
     if (pc) return sort_impl<K, V>(ws, out, out, tmp, vout, vout, vtmp, n, 0, 8 * (int)sizeof(K), BITS, st);
     return sort_impl<K, V>(ws, out, out, tmp, vout, vout, vtmp, n, 0, W, BITS, st, bias);
@@ -4896,9 +5067,23 @@ hipError_t sort_hybrid(Workspace& ws, const K* in, K* out, K* tmp, const V* vin,
 #else
 #define LS_BS_INL(B, I, G, NBP, CAPN, IL, OV, OL) (void)0
 #endif
+      // (lbits == 16: from the u16 array when the last pass was packed)
+#define LS_BC16(B, I, M, G, NBP, CAPN, IL, OV, OL)                                                               \
+  do {                                                                                                           \
+    if constexpr (kP16Ok) {                                                                                      \
+      if (p16) {                                                                                                 \
+        hipLaunchKernelGGL((k_bucket_count<B, (I), Op, M, false, false, true>), dim3(G), dim3(B), 0, st, ci_,    \
+                           co_, bstart, nsize, NBP, CAPN, IL, lbits, bias, OV, OL, ocap_, lsd_n, lsd_l, rty_n,   \
+                           rty_l);                                                                               \
+        break;                                                                                                   \
+      }                                                                                                          \
+    }                                                                                                            \
+    hipLaunchKernelGGL((k_bucket_count<B, (I), Op, M>), dim3(G), dim3(B), 0, st, ci_, co_, bstart, nsize, NBP,   \
+                       CAPN, IL, lbits, bias, OV, OL, ocap_, lsd_n, lsd_l, rty_n, rty_l);                        \
+  } while (0)
 #define LS_BSX(B, I, G, NBP, CAPN, IL, OV, OL)                                                                   \
   if constexpr (C) {                                                                                             \
-    const uint32_t* ci_ = reinterpret_cast<const uint32_t*>(out);                                                \
+    const uint32_t* ci_ = p16 ? reinterpret_cast<const uint32_t*>(p16buf) : reinterpret_cast<const uint32_t*>(out); \
     uint32_t* co_ = reinterpret_cast<uint32_t*>(out);                                                            \
     const uint32_t ocap_ = (OL) == flist ? NB : kListCap;                                                        \
     if (lbits <= 12)                                                                                             \
@@ -4910,11 +5095,9 @@ hipError_t sort_hybrid(Workspace& ws, const K* in, K* out, K* tmp, const V* vin,
     else if (B == 256 && two && inl)                                                                             \
       LS_BS_INL(B, I, G, NBP, CAPN, IL, OV, OL);                                                                 \
     else if (B == 256 && two)                                                                                    \
-      hipLaunchKernelGGL((k_bucket_count<B, (I), Op, kCnt2F>), dim3(G), dim3(B), 0, st, ci_, co_, bstart, nsize, \
-                         NBP, CAPN, IL, lbits, bias, OV, OL, ocap_, lsd_n, lsd_l, rty_n, rty_l);                    \
+      LS_BC16(B, I, kCnt2F, G, NBP, CAPN, IL, OV, OL);                                                           \
     else                                                                                                         \
-      hipLaunchKernelGGL((k_bucket_count<B, (I), Op, kCnt3F>), dim3(G), dim3(B), 0, st, ci_, co_, bstart, nsize, \
-                         NBP, CAPN, IL, lbits, bias, OV, OL, ocap_, lsd_n, lsd_l, rty_n, rty_l);                    \
+      LS_BC16(B, I, kCnt3F, G, NBP, CAPN, IL, OV, OL);                                                           \
   } else if (pcnt) {                                                                                             \
     if constexpr (kPairCnt) {                                                                                    \
       /* (u64, u32) pairs: the counting placement, 1024-thread blocks of at least the slots asked for */         \
@@ -4947,18 +5130,43 @@ hipError_t sort_hybrid(Workspace& ws, const K* in, K* out, K* tmp, const V* vin,
       // grid over the list (none listed: the blocks read the count and exit)
 #define LS_BSL(B, I)                                                                                               \
   if constexpr (C) {                                                                                               \
-    if (two && (!inl || n2 > 0)) {                                                                                 \
-      hipLaunchKernelGGL((k_bucket_count<kRetryBlock, ((I) * 256 + kRetryBlock - 1) / kRetryBlock, Op, kCnt3F, true>), \
-                         dim3(std::min<uint32_t>(NB, (uint32_t)std::max(1, ws.num_cus) * 5)), dim3(kRetryBlock), 0, st, \
-                         reinterpret_cast<const uint32_t*>(out), reinterpret_cast<uint32_t*>(out), bstart, nsize,  \
-                         ctr + 15, NB, flist, lbits, bias, ctr + 10, nullptr, 0u, ctr + 7, flist2, nullptr,        \
-                         nullptr);                                                                                 \
+    constexpr int RI_ = ((I) * 256 + kRetryBlock - 1) / kRetryBlock;                                               \
+    const dim3 rg_(std::min<uint32_t>(NB, (uint32_t)std::max(1, ws.num_cus) * 5));                                 \
+    const dim3 lg_(std::min<uint32_t>(NB, (uint32_t)std::max(1, ws.num_cus) * 2));                                 \
+    bool packed_ = false;                                                                                          \
+    if constexpr (kP16Ok) {                                                                                        \
+      if (p16) {                                                                                                   \
+        /* both lists read the (untouched) u16 array */                                                            \
+        packed_ = true;                                                                                            \
+        if (two && (!inl || n2 > 0)) {                                                                             \
+          hipLaunchKernelGGL((k_bucket_count<kRetryBlock, RI_, Op, kCnt3F, true, false, true>), rg_,               \
+                             dim3(kRetryBlock), 0, st, reinterpret_cast<const uint32_t*>(p16buf),                  \
+                             reinterpret_cast<uint32_t*>(out), bstart, nsize, ctr + 15, NB, flist, lbits, bias,    \
+                             ctr + 10, nullptr, 0u, ctr + 7, flist2, nullptr, nullptr);                            \
+          LS_TRY(hipGetLastError());                                                                               \
+        }                                                                                                          \
+        /* (duplicate-heavy keys list every bucket here: three 256-thread blocks per CU, what its ~130 VGPRs    \
+           hold at once, not two, so the packed sort keeps within 3x of the uniform one, which pack16 made     \
+           faster) */                                                                                              \
+        const dim3 lg16_(std::min<uint32_t>(NB, (uint32_t)std::max(1, ws.num_cus) * ((B) == 256 ? 3u : 2u)));      \
+        hipLaunchKernelGGL((k_bucket_sort<BITS, B, (I), Op, K, V, 0, true, true>), lg16_, dim3(B), 0, st,          \
+                           reinterpret_cast<const K*>(p16buf), out, vout, vout, bstart, nsize, lsd_n, NB, lsd_l,   \
+                           lbits, bias, ctr + 14, nullptr, 0u);                                                    \
+        LS_TRY(hipGetLastError());                                                                                 \
+      }                                                                                                            \
+    }                                                                                                              \
+    if (!packed_) {                                                                                                \
+      if (two && (!inl || n2 > 0)) {                                                                               \
+        hipLaunchKernelGGL((k_bucket_count<kRetryBlock, RI_, Op, kCnt3F, true>), rg_, dim3(kRetryBlock), 0, st,    \
+                           reinterpret_cast<const uint32_t*>(out), reinterpret_cast<uint32_t*>(out), bstart,       \
+                           nsize, ctr + 15, NB, flist, lbits, bias, ctr + 10, nullptr, 0u, ctr + 7, flist2,        \
+                           nullptr, nullptr);                                                                      \
+        LS_TRY(hipGetLastError());                                                                                 \
+      }                                                                                                            \
+      hipLaunchKernelGGL((k_bucket_sort<BITS, B, (I), Op, K, V, 0, true>), lg_, dim3(B), 0, st, out, out, vout,    \
+                         vout, bstart, nsize, lsd_n, NB, lsd_l, lbits, bias, ctr + 14, nullptr, 0u);               \
       LS_TRY(hipGetLastError());                                                                                   \
     }                                                                                                              \
-    hipLaunchKernelGGL((k_bucket_sort<BITS, B, (I), Op, K, V, 0, true>),                                           \
-                       dim3(std::min<uint32_t>(NB, (uint32_t)std::max(1, ws.num_cus) * 2)), dim3(B), 0, st, out,   \
-                       out, vout, vout, bstart, nsize, lsd_n, NB, lsd_l, lbits, bias, ctr + 14, nullptr, 0u);       \
-    LS_TRY(hipGetLastError());                                                                                     \
   } else if constexpr (kPairCnt) {                                                                                 \
     if (pcnt) {                                                                                                    \
       /* the pairs whose 3-bit counts would wrap (8+ equal x; their length <= cap, the planning's bound):        \
@@ -5009,6 +5217,7 @@ hipError_t sort_hybrid(Workspace& ws, const K* in, K* out, K* tmp, const V* vin,
     }
 #undef LS_BSL
 #undef LS_BSX
+#undef LS_BC16
 #undef LS_BS1024
 #undef LS_BS512
 #undef LS_BS2
