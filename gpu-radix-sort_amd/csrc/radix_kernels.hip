@@ -23,6 +23,8 @@
 // consumers instead of a separate pass; scan.cu:16-58 does it as a kernel).
 #include "radix.h"
 
+#include "hybrid_plan.h"
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -35,6 +37,7 @@
 #include <type_traits>
 
 namespace lsort {
+using namespace hplan;
 
 constexpr int kWave = 64;
 
@@ -1181,11 +1184,6 @@ struct HybridGeo {
 // over consecutive dn banks).  FUSE: the tile's row of C is zeroed after use
 // (it becomes the C_next of the pass after the next); otherwise the count
 // kernel rewrites every row.
-#ifdef LIBSORT_TP_WAVES_PER_EU  // A/B knob: occupancy target of the pass kernel
-#define LS_TP_ATTR __attribute__((amdgpu_waves_per_eu(LIBSORT_TP_WAVES_PER_EU)))
-#else
-#define LS_TP_ATTR
-#endif
 // ANY_ORDER (the keys-only MSD hybrid's digit passes): the bucket sort orders
 // every bucket completely afterwards, so a pass need not keep the input order
 // within a digit run; the rank is then one LDS atomic per key instead of the
@@ -1195,7 +1193,7 @@ struct HybridGeo {
 #endif
 template <int BITS, int BLOCK, int ITEMS, typename K, typename V, bool FUSE, typename Op = RadixDigit,
           typename OpN = RadixDigit, int GEO = 0, bool ANY_ORDER = false, int P16 = 0>
-__global__ __launch_bounds__(BLOCK) LS_TP_ATTR void k_tile_pass(const K* __restrict__ kin, K* __restrict__ kout,
+__global__ __launch_bounds__(BLOCK) void k_tile_pass(const K* __restrict__ kin, K* __restrict__ kout,
                                                      const V* __restrict__ vin, V* __restrict__ vout,
                                                      uint32_t n, Op op_in, OpN op_next,
                                                      uint32_t* __restrict__ C, const uint32_t* __restrict__ B,
@@ -1243,11 +1241,9 @@ __global__ __launch_bounds__(BLOCK) LS_TP_ATTR void k_tile_pass(const K* __restr
   // P16 (the last digit pass of a full-width keys-only hybrid sort, "pack16";
   // DESIGN.md section 3): the pass's digit is the last of the key's top 16
   // bits, which the bucket index restates, so only (uint16_t)key is written,
-  // to geo.o16 at the key's element index (nothing to kout).  1: one 2-byte
-  // store per key; 2 (A/B builds only, LIBSORT_PACK16_PAIRED_AB; measured
-  // slower): full tiles write two neighbours of a run
-  // that share a global dword as one dword store (2-byte stores at run heads
-  // and tails).
+  // to geo.o16 at the key's element index (nothing to kout), one 2-byte
+  // store per key (pairing neighbours into dword stores measured slower,
+  // DESIGN.md section 3).
   static_assert(P16 == 0 || (GEO == 1 && !FUSE && ANY_ORDER && sizeof(K) == 4 && !HAS_V && ITEMS % (2 * SPLIT) == 0),
                 "pack16: the keys-only last pass over a tile table");
   static_assert(!RSV || (ANY_ORDER && !HAS_V && (GEO & 2) == 0), "reserved placement: keys-only depth 0");
@@ -1524,42 +1520,7 @@ __global__ __launch_bounds__(BLOCK) LS_TP_ATTR void k_tile_pass(const K* __restr
 
   if constexpr (P16 != 0) {
     uint16_t* const o16 = geo.o16;
-    if (P16 == 2 && full) {
-      // thread m owns local positions a = 2m, b = 2m + 1 and reads their
-      // neighbours p = 2m - 1, x = 2m + 2.  A key at an even global index
-      // takes its successor along in one dword when both are of one run; a key
-      // at an odd global index is written by its predecessor's thread, or
-      // alone when it heads its run.  A dword never leaves the tile's run:
-      // neighbouring tiles and buckets share dwords.
-      constexpr int PAIRS = TILE / 2, PJ = (PAIRS + BLOCK - 1) / BLOCK;
-#pragma unroll
-      for (int j = 0; j < PJ; ++j) {
-        const uint32_t m = tid + j * BLOCK;
-        if (PAIRS % BLOCK == 0 || m < (uint32_t)PAIRS) {
-          const uint2 ab = make_uint2((uint32_t)s_keys[2 * m], (uint32_t)s_keys[2 * m + 1]);
-          const uint32_t da = op((K)ab.x), db = op((K)ab.y);
-          const uint32_t dp = m > 0 ? op(s_keys[2 * m - 1]) : (uint32_t)RADIX;
-          const K kx = 2 * m + 2 < (uint32_t)TILE ? s_keys[2 * m + 2] : (K)0;
-          const uint32_t dx = 2 * m + 2 < (uint32_t)TILE ? op(kx) : (uint32_t)RADIX;
-          const uint32_t ga = ob_base(s_ob[da]) + 2 * m, gb = ob_base(s_ob[db]) + 2 * m + 1;
-          if ((ga & 1u) == 0) {
-            if (da == db)
-              *reinterpret_cast<uint32_t*>(o16 + ga) = (ab.x & 0xFFFFu) | (ab.y << 16);
-            else
-              o16[ga] = (uint16_t)ab.x;
-          } else if (dp != da) {
-            o16[ga] = (uint16_t)ab.x;
-          }
-          if (gb & 1u) {
-            if (da != db) o16[gb] = (uint16_t)ab.y;
-          } else if (dx == db) {
-            *reinterpret_cast<uint32_t*>(o16 + gb) = (ab.y & 0xFFFFu) | ((uint32_t)kx << 16);
-          } else {
-            o16[gb] = (uint16_t)ab.y;
-          }
-        }
-      }
-    } else if (full) {
+    if (full) {
 #pragma unroll
       for (int h = 0; h < SPLIT; ++h) {
         K kk[SP];
@@ -1751,73 +1712,6 @@ __device__ __forceinline__ uint32_t field2_sum(uint32_t w) {
 // cells (kCnt2F: the threads that saw a count wrap; a uniform bucket's
 // overflow is one value with 4 keys: 1-2).
 constexpr uint32_t kRetryMax = 16;
-// kCnt2F's inline retry (INL) of a lightly overflowed bucket (a value with 4+
-// keys wrapped its 2-bit count: ~4% of the uniform 4096-key buckets of a 2^28
-// sort), in the same 24 KB: 3-bit u64 cells over HALF the cell space at a
-// time (2048 cells = 16 KB), each key counted and placed in the half its cell
-// falls in, the second half's starts after the first half's keys.  Sets rk[j]
-// to every key's position; false when a 3-bit count would wrap too (8+ equal
-// keys: the caller lists the bucket for the LSD steps).  Replaces round 4's
-// separate 3-bit LIST launch over those buckets (~45 us per 2^28 sort: two
-// latency-bound rounds of ~20 us buckets).
-template <int BLOCK, int ITEMS, typename ValFn, typename ValidFn>
-__device__ __forceinline__ bool retry3_halves(const uint32_t (&k)[ITEMS], uint32_t (&rk)[ITEMS], uint32_t* s_mem,
-                                              uint32_t* s_wsum, uint32_t lane, ValFn val, ValidFn valid) {
-  constexpr uint32_t HC = kCntCells / 2, PER2 = HC / BLOCK;
-  static_assert(PER2 >= 1 && HC % BLOCK == 0, "half-cells per thread");
-  uint64_t* const s_c = reinterpret_cast<uint64_t*>(s_mem);
-  const uint32_t tid = threadIdx.x;
-  auto ci2 = [&](uint32_t c) -> uint32_t { return (c % PER2) * BLOCK + c / PER2; };
-  uint32_t base = 0;
-#pragma unroll 1
-  for (uint32_t h = 0; h < 2; ++h) {
-    __syncthreads();  // the region's previous use (the 2-bit cells; half 0) is over
-#pragma unroll
-    for (uint32_t q = 0; q < PER2; ++q) s_c[q * BLOCK + tid] = 0ull;
-    __syncthreads();
-    bool ovf = false;
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j)
-      if (valid(j)) {
-        const uint32_t v = val(k[j]), c = v >> 4;
-        if ((c / HC) == h) {
-          const uint32_t sh = 3u * (v & 15u);
-          const uint64_t old = atomicAdd((unsigned long long*)&s_c[ci2(c % HC)], (1ull << sh) + (1ull << 48));
-          rk[j] = (uint32_t)(old >> sh) & 7u;
-          ovf |= rk[j] == 7u;
-        }
-      }
-    if (__any(ovf) && lane == 0) atomicOr((unsigned long long*)&s_c[0], 1ull << 63);
-    __syncthreads();
-    if (s_c[0] >> 63) return false;
-    uint64_t cw[PER2];
-    uint32_t sum = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < PER2; ++q) {
-      cw[q] = s_c[q * BLOCK + tid];
-      sum += (uint32_t)(cw[q] >> 48);
-    }
-    uint32_t total;
-    uint32_t run = block_exclusive_scan<BLOCK>(sum, s_wsum, total) + base;
-#pragma unroll
-    for (uint32_t q = 0; q < PER2; ++q) {
-      s_c[q * BLOCK + tid] = (cw[q] & 0xFFFFFFFFFFFFull) | ((uint64_t)run << 48);
-      run += (uint32_t)(cw[q] >> 48);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j)
-      if (valid(j)) {
-        const uint32_t v = val(k[j]), c = v >> 4;
-        if ((c / HC) == h) {
-          const uint64_t cc = s_c[ci2(c % HC)];
-          rk[j] += (uint32_t)(cc >> 48) + field3_sum(cc & ((1ull << (3u * (v & 15u))) - 1ull));
-        }
-      }
-    base += total;
-  }
-  return true;
-}
 
 // The counting placement works in exactly the cell words (32 KB: five blocks
 // of 256 threads per CU): the overflow flag is a spare bit of a cell word,
@@ -1830,7 +1724,7 @@ __device__ __forceinline__ bool retry3_halves(const uint32_t (&k)[ITEMS], uint32
 // P16 (pack16 input, k_bucket_count): item j = 2q + h is half h of the q-th
 // dword the thread loaded, slot 2 * (w * (ITEMS / 2) * 64 + q * 64 + lane) + h
 // counted from the bucket's dword-aligned floor, start & 1 slots below start.
-template <int BLOCK, int ITEMS, int MODE, typename Op, bool INL = false, bool P16 = false>
+template <int BLOCK, int ITEMS, int MODE, typename Op, bool P16 = false>
 __device__ __forceinline__ uint32_t bucket_count_place(const uint32_t (&k)[ITEMS], uint64_t* s_cw, uint32_t* out,
                                                    uint32_t start, uint32_t len, uint32_t lbits_in, uint32_t bias) {
   constexpr int PER = kCntCells / BLOCK;
@@ -1877,33 +1771,28 @@ __device__ __forceinline__ uint32_t bucket_count_place(const uint32_t (&k)[ITEMS
     const uint64_t bal = __ballot(ovf);
     if (bal && lane == 0) atomicAdd(&s_ws2[BLOCK / kWave], (uint32_t)__popcll(bal));
     __syncthreads();
-    if (const uint32_t sev = s_ws2[BLOCK / kWave]) {
-      // light (a few values with 4+ keys): the 3-bit retry inline (INL);
-      // heavy, or a 3-bit wrap: the caller lists the bucket
-      if (!INL || sev > kRetryMax) return sev;
-      if (!retry3_halves<BLOCK, ITEMS>(k, rk, s_keys, s_ws2, lane, val, valid)) return kRetryMax + 1;
-    } else {
-      uint32_t cnt[PER], sum = 0;
+    // an overflow (a value with 4+ keys): the caller lists the bucket
+    if (const uint32_t sev = s_ws2[BLOCK / kWave]) return sev;
+    uint32_t cnt[PER], sum = 0;
 #pragma unroll
-      for (int q = 0; q < PER; ++q) {
-        cnt[q] = field2_sum(s_w[q * BLOCK + tid]);
-        sum += cnt[q];
-      }
-      uint32_t total;
-      uint32_t run = block_exclusive_scan<BLOCK>(sum, s_ws2, total);
-#pragma unroll
-      for (int q = 0; q < PER; ++q) {
-        s_st[q * BLOCK + tid] = (uint16_t)run;
-        run += cnt[q];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int j = 0; j < ITEMS; ++j)
-        if (valid(j)) {
-          const uint32_t v = val(k[j]), c = ci(v >> 4);
-          rk[j] += (uint32_t)s_st[c] + field2_sum(s_w[c] & ((1u << (2u * (v & 15u))) - 1u));
-        }
+    for (int q = 0; q < PER; ++q) {
+      cnt[q] = field2_sum(s_w[q * BLOCK + tid]);
+      sum += cnt[q];
     }
+    uint32_t total;
+    uint32_t run = block_exclusive_scan<BLOCK>(sum, s_ws2, total);
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      s_st[q * BLOCK + tid] = (uint16_t)run;
+      run += cnt[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j)
+      if (valid(j)) {
+        const uint32_t v = val(k[j]), c = ci(v >> 4);
+        rk[j] += (uint32_t)s_st[c] + field2_sum(s_w[c] & ((1u << (2u * (v & 15u))) - 1u));
+      }
   } else if constexpr (MODE != kCntSmall) {
 #pragma unroll
     for (int q = 0; q < PER; ++q) s_cw[q * BLOCK + tid] = 0ull;
@@ -2023,7 +1912,7 @@ __device__ __forceinline__ uint32_t bucket_count_place(const uint32_t (&k)[ITEMS
 // elements per lane per load, the elements outside the bucket masked (an odd
 // start takes one slot more than len: the block has 2 * ceil(ITEMS / 2) slots
 // per thread).  in != out, so an overflowed bucket's input stays as it was.
-template <int BLOCK, int ITEMS, typename Op, int MODE, bool LIST = false, bool INL = false, bool P16 = false>
+template <int BLOCK, int ITEMS, typename Op, int MODE, bool LIST = false, bool P16 = false>
 __global__ __launch_bounds__(BLOCK)
 __attribute__((amdgpu_waves_per_eu(
     BLOCK >= 1024 && ITEMS <= 17 && MODE != kCntSmall ? 8 : (BLOCK == 256 && ITEMS <= 17 && MODE == kCntSmall) ? 7 : 1,
@@ -2063,7 +1952,7 @@ void k_bucket_count(const uint32_t* in, uint32_t* out, const uint32_t* __restric
         k[2 * q] = hb | (x & 0xFFFFu);
         k[2 * q + 1] = hb | (x >> 16);
       }
-      sev = bucket_count_place<BLOCK, 2 * ND, MODE, Op, INL, true>(k, s_cw, out, start, len, lbits, bias);
+      sev = bucket_count_place<BLOCK, 2 * ND, MODE, Op, true>(k, s_cw, out, start, len, lbits, bias);
     } else {
       uint32_t k[ITEMS];
 #pragma unroll
@@ -2071,10 +1960,10 @@ void k_bucket_count(const uint32_t* in, uint32_t* out, const uint32_t* __restric
         const uint32_t i = wbase + j * kWave + lane;
         k[j] = i < len ? load_stream(&in[(size_t)start + i]) : 0u;
       }
-      sev = bucket_count_place<BLOCK, ITEMS, MODE, Op, INL>(k, s_cw, out, start, len, lbits, bias);
+      sev = bucket_count_place<BLOCK, ITEMS, MODE, Op>(k, s_cw, out, start, len, lbits, bias);
     }
     if (sev && threadIdx.x == 0) {  // (in == out keeps the bucket for the next try)
-      if (!INL && retry_list && sev <= kRetryMax)
+      if (retry_list && sev <= kRetryMax)
         retry_list[atomicAdd(retry_n, 1u)] = b;
       else
         ovf_list[atomicAdd(ovf_n, 1u)] = b;
@@ -2684,11 +2573,6 @@ __global__ __launch_bounds__(256) void k_hyb_expand(const uint32_t* __restrict__
 // Its capacity comes from a stratified sample of the range; a tile that finds
 // its slice full writes nothing and raises a flag, and the host then runs the
 // LSD sort from the untouched input (sort_hybrid).
-constexpr int kRsvRanges = 8;
-// hyb_host word the samplers raise to the sort's sequence number after their
-// size estimates (the host polls it instead of recording an event)
-constexpr uint32_t kHybSeqWord = 511;
-constexpr uint32_t kHybSeqWord2 = 510;  // k_hyb_children's, after the bucket stats
 
 // Waits until the pinned word *w == v (a kernel's system-scope store): a
 // pause spin for the first ~100 us (the usual wait: the word arrives while the
@@ -2727,7 +2611,6 @@ inline hipError_t wait_host_word(const uint32_t* w, uint32_t v, hipStream_t st) 
   std::atomic_thread_fence(std::memory_order_acquire);
   return hipSuccess;
 }
-constexpr int kRsvBlocks = 32;  // sampling blocks per range
 // samples per thread: 4 for 4-bit digits (32768 per range, ~2048 per slice),
 // 16 for 8-bit (131072 per range, ~512 per slice)
 template <int RADIX> constexpr int rsv_per_thread() { return RADIX >= 256 ? 16 : 4; }
@@ -3905,8 +3788,8 @@ hipError_t Workspace::ensure_tiles(size_t count_words, size_t chunk_words) {
 hipError_t Workspace::ensure_hybrid(size_t words) {
   if (!hyb_evt) LS_TRY(hipEventCreateWithFlags(&hyb_evt, hipEventDisableTiming));
   if (!hyb_host) {
-    LS_TRY(hipHostMalloc(&hyb_host, 512 * sizeof(uint32_t), hipHostMallocDefault));
-    std::memset(hyb_host, 0, 512 * sizeof(uint32_t));  // (the sequence word starts below every sort's)
+    LS_TRY(hipHostMalloc(&hyb_host, kHostWords * sizeof(uint32_t), hipHostMallocDefault));
+    std::memset(hyb_host, 0, kHostWords * sizeof(uint32_t));  // (the sequence word starts below every sort's)
   }
   if (words <= hyb_cap) return hipSuccess;
   if (hyb) { (void)hipFree(hyb); hyb = nullptr; }
@@ -4200,18 +4083,10 @@ inline int rsv_mode() {
 // pack16 (sort_hybrid): the last digit pass of a full-width keys-only sort
 // writes 16-bit keys and the bucket kernels read them.  LIBSORT_HYB_PACK16=0
 // keeps whole keys; anything else, or unset: on.  Read per call (the tests
-// switch it in process).  An A/B build (-DLIBSORT_PACK16_PAIRED_AB=1) also
-// holds the last pass's paired dword stores, picked by =b (2-byte stores: =a):
-// 2.04-2.06 against 2.03-2.04 ms per 2^28-key sort, 1.56 against 1.50 ms at
-// 8-bit digits, 3 interleaved runs each (profiles/pack16_ab.txt), so the
-// product build does not instantiate it.
-#ifndef LIBSORT_PACK16_PAIRED_AB
-#define LIBSORT_PACK16_PAIRED_AB 0
-#endif
+// switch it in process).
 inline int pack16_mode() {
   const char* s = getenv("LIBSORT_HYB_PACK16");
-  if (!s) return 1;
-  return s[0] == '0' ? 0 : (LIBSORT_PACK16_PAIRED_AB && s[0] == 'b') ? 2 : 1;
+  return s && s[0] == '0' ? 0 : 1;
 }
 
 // The 2-bit counting cells for 256-thread bucket blocks (kCnt2F);
@@ -4220,23 +4095,6 @@ inline bool bucket2_on() {
   static const bool on = [] {
     const char* s = getenv("LIBSORT_BUCKET2");
     return !(s && s[0] == '0');
-  }();
-  return on;
-}
-
-// kCnt2F's lightly overflowed buckets retried inline with 3-bit half cells
-// (retry3_halves) instead of by a LIST launch: an A/B build only
-// (-DLIBSORT_BUCKET2_INLINE_AB=1, then LIBSORT_BUCKET2_INLINE=1): measured
-// 449 -> 956 us for the bucket phase of a 2^28 sort, 3 interleaved runs each,
-// profiles/r05d_bucket2_inline_ab.txt -- the rarely taken branch costs every
-// block its registers and occupancy.  The product build does not instantiate it.
-#ifndef LIBSORT_BUCKET2_INLINE_AB
-#define LIBSORT_BUCKET2_INLINE_AB 0
-#endif
-inline bool bucket2_inline_on() {
-  static const bool on = [] {
-    const char* s = getenv("LIBSORT_BUCKET2_INLINE");
-    return LIBSORT_BUCKET2_INLINE_AB && s && s[0] == '1';
   }();
   return on;
 }
@@ -4308,12 +4166,6 @@ hipError_t tiles_counts_u8(Workspace& ws, size_t n, uint32_t rows, uint32_t* C, 
   return hipGetLastError();
 }
 
-// A/B build only (-DLIBSORT_AB_LSD_ANY_ORDER=1): the LSD passes rank by LDS
-// atomics like the hybrid's (NOT stable: wrong partial sorts) -- the price of
-// the stable ballot rank, for timing.
-#ifndef LIBSORT_AB_LSD_ANY_ORDER
-#define LIBSORT_AB_LSD_ANY_ORDER 0
-#endif
 template <int BITS, typename K, typename V, typename Op = RadixDigit>
 hipError_t tiles_pass(Workspace& ws, const K* kin, K* kout, const V* vin, V* vout, size_t n, int p, int P,
                       int lo, int hi, hipStream_t st, uint32_t bias = 0) {
@@ -4353,11 +4205,9 @@ hipError_t tiles_pass(Workspace& ws, const K* kin, K* kout, const V* vin, V* vou
                        kin, kout, vin, vout, (uint32_t)n, op, op_next, cur, ws.tb, tiles_digit_starts(ws, tiles, BITS),
                        nxt, HybridGeo{});
   else
-    hipLaunchKernelGGL((k_tile_pass<BITS, B, tp_items<K, V>(BITS), K, V, false, Op, Op, 0,
-                                    LIBSORT_AB_LSD_ANY_ORDER && std::is_same<V, NoValue>::value>),
-                       dim3(tiles), dim3(B), 0, st, kin,
-                       kout, vin, vout, (uint32_t)n, op, op_next, cur, ws.tb, tiles_digit_starts(ws, tiles, BITS),
-                       nxt, geo);
+    hipLaunchKernelGGL((k_tile_pass<BITS, B, tp_items<K, V>(BITS), K, V, false, Op, Op, 0, false>), dim3(tiles),
+                       dim3(B), 0, st, kin, kout, vin, vout, (uint32_t)n, op, op_next, cur, ws.tb,
+                       tiles_digit_starts(ws, tiles, BITS), nxt, geo);
   return hipGetLastError();
 }
 
@@ -4614,15 +4464,6 @@ struct HybPieces {
   const uint32_t* seghi = nullptr;
 };
 
-// Words of the reserved depth 0's slices: n keys plus each slice's sampled
-// slack (k_rsv_sample: (s + 5 sqrt(s) + 24) N / S per slice, rounded up to
-// whole tiles), over NS = nc * 8 slices, S samples per range: at most
-// n (1 + 5 sqrt(nc / S) + 25 nc / S) + NS * TILE.
-inline size_t rsv_capacity_bound_nc(size_t n, uint32_t nc, uint32_t S, uint32_t tile) {
-  const double f = 5.0 * std::sqrt((double)nc / S) + 25.0 * nc / S;
-  return n + (size_t)std::ceil((double)n * f) + (size_t)nc * kRsvRanges * tile + 1024;
-}
-
 // Depth 0 of a pre-partitioned input: tile t of piece p (first tile w <= t <
 // next piece's first tile) = (off + k * TILE, min(TILE, len - k * TILE), seg),
 // k = t - w (binary search over the pieces); the segments' first tiles and
@@ -4647,583 +4488,579 @@ __global__ __launch_bounds__(256) void k_hyb_pieces(const uint4* __restrict__ pi
   tiles[t] = make_uint4(pc.x + k * TILE, min((uint32_t)TILE, pc.y - k * TILE), pc.z, t);
 }
 
-template <int BITS, typename Op, typename K = uint32_t, typename V = NoValue>
-hipError_t sort_hybrid(Workspace& ws, const K* in, K* out, K* tmp, const V* vin, V* vout, V* vtmp, size_t n, int W,
-                       uint32_t bias, hipStream_t st, bool* handled, uint64_t span = 0,
-                       const HybPieces* pc = nullptr) {
-  constexpr int RADIX = 1 << BITS;
+// One hybrid sort: its plan, its workspace pointers and sort_hybrid's stages
+// (set-up, the reserved depth 0 or a counted depth per digit, the bucket phase).
+template <int BITS, typename Op, typename K, typename V>
+struct HybridSort {
+  static constexpr int RADIX = 1 << BITS;
   // depths >= 1 (tiles from a table) and depth 0 of a whole array (tiles
   // computed: B0 threads, TILE0 keys; the same but for (u64, u32) pairs)
-  constexpr int B = tp_block_tab<K, V>(BITS);
-  constexpr int ITEMS = tp_items<K, V>(BITS);
-  constexpr int TILE = B * ITEMS;
-  constexpr int B0 = tp_block<K, V>(BITS);
-  constexpr int TILE0 = B0 * ITEMS;
+  static constexpr int B = tp_block_tab<K, V>(BITS);
+  static constexpr int ITEMS = tp_items<K, V>(BITS);
+  static constexpr int TILE = B * ITEMS;
+  static constexpr int B0 = tp_block<K, V>(BITS);
+  static constexpr int TILE0 = B0 * ITEMS;
   static_assert(TILE0 == TILE || !std::is_same<V, NoValue>::value, "keys-only: one tile size");
-  // digit passes: 16 / BITS over the top 16 of the W bits, or (pieces) the
-  // caller's count; the last one writes out: depth k writes out when
-  // depths - 1 - k is even, tmp otherwise (depth 0 reads in)
-  const int DEPTHS = pc ? pc->depths : 16 / BITS;
-  const uint32_t nseg0 = pc ? pc->nseg : 1u;  // segments entering depth 0
-  const uint64_t NB64 = (uint64_t)nseg0 << (BITS * DEPTHS);  // buckets
-  if (DEPTHS < 1 || NB64 > (1ull << 22) || (pc && (const void*)in == (const void*)out)) return hipErrorInvalidValue;
-  const uint32_t NB = (uint32_t)NB64;
-  const uint32_t lbits = (uint32_t)(W - BITS * DEPTHS);  // bits the bucket sort orders
-  *handled = false;
-  // bucket-sort blocks (256 x items keys), in two sizes: the first holds the
-  // mean bucket of uniform keys + 3.5 sigma (all but a few of the 65536
-  // buckets), those few are listed for the second, 6 x 256 keys larger.
-  // Classes: first size 9 / 13 / 17 / 19 keys per thread.
-  constexpr uint32_t kListCap = 1024;
-  // a range sort's keys lie in [bias, bias + span), span in (2^(W-1), 2^W]:
-  // only the first span / 2^(W-16) of the 16-bit prefixes (and span / 2^(W-BITS)
-  // of the top digits) are populated, each by n * 2^(W-16) / span keys on
-  // average (range rounds of the multi-GPU sort: a W = 27 round spans ~0.8 of
-  // 2^27, which the full-width shares would take for skew)
-  const double fill = pc ? pc->fill : span ? (double)span / std::ldexp(1.0, W) : 1.0;
-  const double mean = (double)n / (NB * fill);
-  const double need = mean + 3.5 * std::sqrt(mean);
-  // class 4 (32-bit keys): 512-thread blocks of 17 keys per thread for
-  // buckets of ~8K keys (full sorts up to 2^29 + 2^23 keys); class 5 (32-bit
-  // keys without values, the counting placement only): 1024 x 17 for ~16K
-  // keys (2^30-key sorts: configs[2]); without it such a sort takes the LSD
-  // passes.  libsortSetBucketMode(0) / LIBSORT_BUCKET_COUNT=0 keeps the LSD
-  // steps.
-  constexpr bool kCntOk = sizeof(K) == 4 && std::is_same<V, NoValue>::value;
-  const bool cnt = kCntOk && get_bucket_mode() == 1 && W - BITS * DEPTHS <= 16;
-  const int cls = need <= 256.0 * 9 ? 0 : need <= 256.0 * 13 ? 1 : need <= 256.0 * 17 ? 2 :
-                  (need <= 256.0 * 19 || sizeof(K) == 8) ? 3 : need <= 256.0 * 34 ? 4 : 5;
-  if (cls == 5 && !cnt) return hipSuccess;  // (not handled: the LSD sort)
-  static constexpr int kItems1[6] = {9, 13, 17, 19, 34, 68};  // per 256 threads
-  // the two blocks' slots (64-bit keys: 512-thread blocks, keys per thread
-  // rounded up)
-  constexpr int BB = sizeof(K) == 8 ? LIBSORT_BUCKET64_BLOCK : 256;
-  const int BBc = cls == 5 ? 1024 : cls == 4 ? 512 : BB;
-  const int extra = cls == 5 ? 24 : cls == 4 ? 12 : 6;  // second block: 6 (12, 24) x 256 more slots
-  const uint32_t cap1 = (uint32_t)BBc * (((uint32_t)kItems1[cls] * 256u + BBc - 1) / BBc);
-  const uint32_t cap = (uint32_t)BBc * (((uint32_t)(kItems1[cls] + extra) * 256u + BBc - 1) / BBc);
-  const uint32_t T0 = pc ? pc->tiles : (uint32_t)((n + TILE0 - 1) / TILE0);  // depth 0's tiles
-  const uint32_t Tt = pc ? pc->tiles : (uint32_t)((n + TILE - 1) / TILE);    // n in table-depth tiles
-  // reserved depth 0 (32-bit keys only, in != out: the fallback re-reads in):
-  // no count pass; depth 0 writes slices of ws.rsv (tile rows of depth 1
-  // numbered by slice capacity, at most tb1)
-  // (pieces: slices per (segment, digit, range), at most kRsvMaxSlices)
-  constexpr bool kRsvOk = sizeof(K) == 4 && std::is_same<V, NoValue>::value;
-  const uint32_t rnc = (pc ? nseg0 : 1u) * (uint32_t)RADIX;  // children of depth 0
-  const uint32_t rns = rnc * kRsvRanges;                      // slices
-  int rmode = kRsvOk && DEPTHS > 1 && (const void*)in != (const void*)out && (!pc || (pc->cum && rns <= kRsvMaxSlices))
-                  ? rsv_mode()
-                  : 0;
-  const int rper = rsv_pc_per(rnc);
-  const size_t rbound = pc ? rsv_capacity_bound_nc(n, rnc, kRsvBlocks * 256 * rper, TILE)
-                           : rsv_capacity_bound(n, BITS);
-  const uint32_t tb1 = (uint32_t)((rbound + TILE - 1) / TILE) + rns;
-  // the cursors after the slices, 256-byte aligned (8-bit: 64-bit adds)
-  const size_t rcur_off = (rbound + 63) & ~(size_t)63;
-  // The slices (~1.14 n words at 4-bit digits, ~1.28 n at 8-bit) stay cached
-  // in the workspace like its other buffers (grow-only, freed by
-  // libsortRelease).  If they cannot be allocated, depth 0 takes the count
-  // pass instead: the sort needs no more memory than before.
-  // (LIBSORT_HYB_RESERVE=nomem: as if the allocation failed -- tests)
-  if (rmode == 3 || (rmode && ws.ensure_rsv(rcur_off + (size_t)rns * kRsvCurStride) != hipSuccess)) {
-    (void)hipGetLastError();
-    rmode = 0;
-  }
-  const bool rsv = rmode != 0;
-  // pack16: after the last digit pass of a full-width
-  // sort every key sits in the bucket of its top 16 bits and the bucket index
-  // is that prefix, so the last pass writes only the low 16 bits (2 B per key
-  // instead of 4) and the bucket kernels read them back (2 instead of 4): 36
-  // instead of 40 B per key and sort.  The u16 array (element i = out's
-  // element i) goes to a buffer that is neither the last pass's source nor
-  // out: the slices of the reserved depth 0, which depth 1 has consumed (n / 2
-  // words, below the cursors), or tmp when the last pass reads the slices (two
-  // depths).  Needs the counting placement and the reserved depth 0 (not its
-  // test mode with short slices, whose overflow abandons the later depths).
-  constexpr bool kP16Ok = kCntOk && std::is_same<Op, RadixDigit>::value;
-  const int p16 = (kP16Ok && !pc && W == 32 && lbits == 16 && cnt && rmode == 1) ? pack16_mode() : 0;
-  uint16_t* const p16buf =
-      !p16 ? nullptr : DEPTHS >= 3 ? reinterpret_cast<uint16_t*>(ws.rsv) : reinterpret_cast<uint16_t*>(tmp);
-  // 24-bit pieces are read by the reserved depth 0 only: otherwise the
-  // caller's gather (which unpacks them) and LSD sort
-  if (pc && pc->i8 && !rsv) return hipSuccess;
-  uint32_t rseq = 0;  // the sampler's sequence word (wait_host_word)
-  uint32_t sseq = 0;  // the last depth's children (bucket stats)
-  // segments of depth k (each child has at most one partial tile)
-  auto nseg_at = [&](int k) { return nseg0 << (BITS * k); };
-  auto tbound = [&](int k) { return k == 0 ? T0 : (k == 1 && rsv) ? tb1 : Tt + nseg_at(k); };
-  uint32_t TB = 0;
-  for (int k = 0; k < DEPTHS; ++k) TB = std::max(TB, tbound(k));
-  LS_TRY(ws.ensure_tiles((size_t)TB * RADIX, ((size_t)tp_chunks(TB, BITS) + 1) * RADIX));
-  // hybrid block: tiles[2] | segbase | cstart[2] | nsize | ctile0[2] | ntl | counters
-  const size_t w_tiles = (size_t)TB * 4;
-  const size_t rsv_words = (size_t)kRsvRanges * kRsvBlocks * rnc + 3 * (size_t)rns + 16;
-  const size_t words =
-      2 * w_tiles + NB + 2 * (size_t)NB + NB + 2 * ((size_t)NB + 1) + NB + 16 + kListCap + NB + NB + rsv_words;
-  LS_TRY(ws.ensure_hybrid(words));
-  uint32_t* h = ws.hyb;
-  uint4* tiles[2] = {reinterpret_cast<uint4*>(h), reinterpret_cast<uint4*>(h + w_tiles)};
-  h += 2 * w_tiles;
-  uint32_t* segbase = h; h += NB;
-  uint32_t* cstart[2] = {h, h + NB}; h += 2 * (size_t)NB;
-  uint32_t* nsize = h; h += NB;
-  uint32_t* ctile0[2] = {h, h + NB + 1}; h += 2 * ((size_t)NB + 1);
-  uint32_t* ntl = h; h += NB;
-  uint32_t* ctr = h;  // [k] tiles of depth k (k <= 4), [7] the LSD-step list after 2-bit cells (flist2),
-                      // [8] buckets over the first block, [9] bucket count, [10] over the
-                      // second, [11] largest bucket, [12] buckets over the first block (planning),
-                      // [13] largest child of depth 0 (pieces), [14] reserved depth 0 overflow,
-                      // [15] buckets whose counting placement overflowed
-  h += 16;
-  uint32_t* olist = h;  // the buckets over the first block (kListCap)
-  h += kListCap;
-  uint32_t* flist = h;  // the buckets whose counting placement overflowed (ctr[15] of NB)
-  h += NB;
-  uint32_t* flist2 = h;  // kCnt2F: the buckets for the LSD steps (ctr[7] of NB)
-  h += NB;
-  // reserved depth 0: sample partials | slices (start | capacity | first tile,
-  // + the tile count) | cursors | estimated digit sizes; ctr[14] = overflow
-  uint32_t* rpart = h; h += (size_t)kRsvRanges * kRsvBlocks * rnc;
-  uint32_t* rslice = h; h += 3 * (size_t)rns + 16;
-  uint32_t* rcur = rsv ? ws.rsv + rcur_off : nullptr;  // kRsvCurStride apart
-  uint32_t* Cn0 = ws.tc[1];  // depth 1's count rows (the fused counts of depth 0)
-  if (!rsv) {  // (reserved depth 0: k_rsv_sample sets them)
-    hipLaunchKernelGGL(k_hyb_init, dim3(1), dim3(64), 0, st, ctr, NB);  // one launch, not two memsets (4 fills)
-    LS_TRY(hipGetLastError());
-  } else {
-    // Reserved depth 0: sample -> slices (the depth-0 pass reserves its runs
-    // in them; the next depth's tiles and child starts from the cursors)
-    const Op op0 = make_digit<Op>((uint32_t)(W - BITS), (uint32_t)RADIX - 1u, bias);
-    ScopedTimer tm("rsvsample", st, n);
-    rseq = ++ws.hyb_seq;
-    if (pc) {
-      auto smp = rper == 4 ? k_rsv_sample_pc<RADIX, TILE, 4, Op>
-                 : rper == 8 ? k_rsv_sample_pc<RADIX, TILE, 8, Op> : k_rsv_sample_pc<RADIX, TILE, 16, Op>;
-      hipLaunchKernelGGL(smp, dim3(kRsvRanges * kRsvBlocks), dim3(256), 0, st,
-                         reinterpret_cast<const uint32_t*>(in), pc->i8, reinterpret_cast<const uint4*>(pc->dev), pc->cum,
-                         pc->np, nseg0, T0, (uint32_t)n, op0, rpart, rslice, rcur, ws.hyb_host, Cn0,
-                         BITS == 4 ? tb1 * (uint32_t)RADIX : 0u, ws.tticket + 32, ctr, NB, rmode == 2, rseq);
-    } else {
-      hipLaunchKernelGGL((k_rsv_sample<RADIX, TILE, Op>), dim3(kRsvRanges * kRsvBlocks), dim3(256), 0, st,
-                         reinterpret_cast<const uint32_t*>(in), (uint32_t)n, T0, op0, rpart, rslice, rcur,
-                         ws.hyb_host, Cn0, BITS == 4 ? tb1 * (uint32_t)RADIX : 0u, ws.tticket + 32, ctr, NB,
-                         rmode == 2, rseq);
-    }
-    LS_TRY(hipGetLastError());
-  }
-  if (pc) {
-    // depth 0's tile table and parent arrays from the piece table
-    const uint32_t g = std::max(T0, pc->nseg + 1);
-    hipLaunchKernelGGL((k_hyb_pieces<TILE>), dim3((g + 255) / 256), dim3(256), 0, st,
-                       reinterpret_cast<const uint4*>(pc->dev), pc->np, pc->dev + 4 * (size_t)pc->np, pc->nseg, T0,
-                       tiles[0], ctile0[0], cstart[0], ctr);
-    LS_TRY(hipGetLastError());
-  }
-  const bool dstream = BITS == 8 && dstream_on() && (sizeof(K) == 8 || (kRsvOk && !pc && dstream_u32_on()));
-  // (reserved depth 0: the stream in the slices' coordinates)
-  if (dstream) LS_TRY(ws.ensure_dstream(rsv ? std::max(n, rcur_off) : n));
-  ws.part_pending.valid = false;
-
   // keys only: the passes may reorder within a run (k_tile_pass ANY_ORDER)
-  constexpr bool kAnyOrder = std::is_same<V, NoValue>::value;
-  auto buf = [&](int k) -> K* {
-    return k == 0 ? const_cast<K*>(in) : (k == 1 && rsv) ? reinterpret_cast<K*>(ws.rsv) : ((DEPTHS - k) & 1) ? tmp : out;
+  static constexpr bool kAnyOrder = std::is_same<V, NoValue>::value;
+  // 32-bit keys alone: the counting placement, the reserved depth 0, pack16
+  static constexpr bool kCntOk = sizeof(K) == 4 && std::is_same<V, NoValue>::value;
+  static constexpr bool kP16Ok = kCntOk && std::is_same<Op, RadixDigit>::value;
+  // 64-bit keys: 512-thread bucket blocks (BB; half the keys per thread: 152 ->
+  // ~90 VGPRs for (u64, u32) pairs at 17 slots per 256), on-chip steps over the
+  // top 16 of the 48 bucket bits, then the tie fix-up (k_bucket_sort FIX)
+  static constexpr int BB = sizeof(K) == 8 ? LIBSORT_BUCKET64_BLOCK : 256;
+  static constexpr int FIXB = sizeof(K) == 8 ? LIBSORT_BUCKET64_FIX : 0;
+  static constexpr bool kPairCnt = sizeof(K) == 8 && std::is_same<V, uint32_t>::value && FIXB > 0;
+
+  Workspace& ws;  // (sort_hybrid's arguments)
+  const K* in;
+  K *out, *tmp;
+  const V* vin;
+  V *vout, *vtmp;
+  size_t n;
+  int W;
+  uint32_t bias;
+  hipStream_t st;
+  uint64_t span;
+  const HybPieces* pc;
+  // the plan (setup).  DEPTHS digit passes: 16 / BITS over the top 16 of the W
+  // bits, or (pieces) the caller's count; nseg0 segments enter depth 0; NB
+  // buckets, whose sort orders lbits bits, by the counting placement (cnt)
+  int DEPTHS = 0, p16 = 0;
+  uint32_t nseg0 = 1, NB = 0, lbits = 0;
+  double fill = 1.0;
+  bool cnt = false, rsv = false, dstream = false;
+  BucketPlan bp{};
+  uint32_t T0 = 0, Tt = 0;             // depth 0's tiles; n in table-depth tiles
+  uint32_t rnc = 0, rns = 0, tb1 = 0;  // reserved depth 0: children, slices, depth 1's tile rows
+  size_t rcur_off = 0;
+  uint16_t* p16buf = nullptr;
+  uint32_t rseq = 0, sseq = 0;  // sequence words: the sampler's, the last depth's children's (bucket stats)
+  uint4* tiles[2] = {};  // the hybrid block (hyb_layout) and the reserved slices' cursors
+  uint32_t *segbase = nullptr, *cstart[2] = {}, *nsize = nullptr, *ctile0[2] = {}, *ntl = nullptr, *ctr = nullptr,
+           *olist = nullptr, *flist = nullptr, *flist2 = nullptr, *rpart = nullptr, *rslice = nullptr, *rcur = nullptr;
+  const uint32_t* bstart = nullptr;  // the bucket phase's lists (bucket_phase)
+  uint32_t n2 = 0, *lsd_n = nullptr, *lsd_l = nullptr, *rty_n = nullptr, *rty_l = nullptr;
+  bool two = false, pcnt = false;
+
+  // segments of depth k (each child has at most one partial tile)
+  uint32_t nseg_at(int k) const { return nseg0 << (BITS * k); }
+  uint32_t tbound(int k) const { return tile_bound(k, T0, Tt, tb1, rsv, nseg_at(k)); }
+  K* at(Buf b) const {
+    return b == Buf::In ? const_cast<K*>(in) : b == Buf::Rsv ? reinterpret_cast<K*>(ws.rsv) : b == Buf::Tmp ? tmp : out;
+  }
+  K* buf(int k) const { return at(key_buf(k, DEPTHS, rsv)); }
+  V* vbuf(int k) const {
+    const Buf b = val_buf(k, DEPTHS);
+    return b == Buf::In ? const_cast<V*>(vin) : b == Buf::Tmp ? vtmp : vout;
+  }
+
+  // What depth k works on (tab: its tiles come from a table; m: children)
+  struct Depth {
+    bool last, tab;
+    uint32_t rows, nseg, m;
+    Op op, op_next;
+    uint32_t *C, *Cn;
+    const K* src;
+    K* dst;
+    const V* vsrc;
+    V* vdst;
   };
-  auto vbuf = [&](int k) -> V* { return k == 0 ? const_cast<V*>(vin) : ((DEPTHS - k) & 1) ? vtmp : vout; };
-  for (int k = 0; k < DEPTHS; ++k) {
+  Depth depth(int k) const {
     const bool last = k == DEPTHS - 1;
-    const bool tab = k > 0 || pc;  // this depth's tiles come from a table
-    const uint32_t rows = tbound(k);
-    const uint32_t nseg = nseg_at(k);
-    const uint32_t m = nseg * RADIX;  // children
-    const Op op = make_digit<Op>((uint32_t)(W - BITS * (k + 1)), (uint32_t)RADIX - 1u, bias);
-    const Op op_next = make_digit<Op>((uint32_t)(last ? 0 : W - BITS * (k + 2)), (uint32_t)RADIX - 1u, bias);
-    uint32_t* C = (BITS == 4) ? ws.tc[k & 1] : ws.tc[0];
-    uint32_t* Cn = ws.tc[(k + 1) & 1];
-    const K* src = buf(k);
-    K* dst = buf(k + 1);
-    const V* vsrc = vbuf(k);
-    V* vdst = vbuf(k + 1);
-    if constexpr (kRsvOk) {
-      if (k == 0 && rsv) {
-        // Reserved depth 0 (sampled above): the pass reserves its runs in the
-        // slices; the next depth's tiles and child starts from the cursors
-        HybridGeo g0{tiles[0], ctr, nullptr, nullptr, nullptr, rcur, rslice, ctr + 14, rns};
-        if (dstream && !last) g0.dout = ws.dstream;  // (the next depth's digits, slice positions)
-        if (pc) {
-          g0.i16 = pc->i16;
-          g0.i8 = pc->i8;
-          g0.seghi = pc->seghi;
-        }
-        {
-          ScopedTimer tm("tilepass", st, n);
-          if (pc)
-            hipLaunchKernelGGL((k_tile_pass<BITS, B, ITEMS, K, V, BITS == 4, Op, Op, 5, true>), dim3(T0), dim3(B), 0,
-                               st, src, dst, vsrc, vdst, (uint32_t)n, op, op_next, C, ws.tb, segbase, Cn, g0);
-          else
-            hipLaunchKernelGGL((k_tile_pass<BITS, B, ITEMS, K, V, BITS == 4, Op, Op, 4, true>), dim3(T0), dim3(B), 0,
-                               st, src, dst, vsrc, vdst, (uint32_t)n, op, op_next, C, ws.tb, segbase, Cn, g0);
-          LS_TRY(hipGetLastError());
-        }
-        {
-          ScopedTimer tm("hybplan", st, m);
-          hipLaunchKernelGGL((k_rsv_tiles<RADIX, TILE, BITS == 4>), dim3((tb1 + 255) / 256), dim3(256), 0, st, rslice,
-                             rcur, ctr + 14, tb1, tiles[1], cstart[1], ctile0[1], ctr + 1, Cn, rnc);
-          LS_TRY(hipGetLastError());
-        }
-        // skew check on the sampled digit (pieces: child) sizes (the pass
-        // keeps the GPU busy; it wrote only ws.rsv, so abandoning leaves in
-        // intact).  The sampler raised its sequence word in the pinned
-        // mirror after the sizes: polled, not an event (an event record
-        // stalls the stream ~6 us).
-        LS_TRY(wait_host_word(ws.hyb_host + kHybSeqWord, rseq, st));
-        if (pc) {
-          if ((double)ws.hyb_host[0] / (double)(1ull << (BITS * (DEPTHS - 1))) > 0.9 * cap) return hipSuccess;
-        } else {
-          uint32_t mx = 0;
-          for (int d = 0; d < RADIX; ++d) mx = std::max(mx, ws.hyb_host[d]);
-          const double share = (double)n / (RADIX * fill);
-          if ((double)mx > 1.25 * share + 4.0 * std::sqrt(share) + 32.0 ||
-              (double)mx / (double)(NB / RADIX) > 0.9 * cap)
-            return hipSuccess;
-        }
-        continue;
-      }
+    const uint32_t mask = (uint32_t)RADIX - 1u;
+    return Depth{last, k > 0 || pc, tbound(k), nseg_at(k), nseg_at(k) * RADIX,
+                 make_digit<Op>((uint32_t)(W - BITS * (k + 1)), mask, bias),
+                 make_digit<Op>((uint32_t)(last ? 0 : W - BITS * (k + 2)), mask, bias),
+                 (BITS == 4) ? ws.tc[k & 1] : ws.tc[0], ws.tc[(k + 1) & 1], buf(k), buf(k + 1), vbuf(k), vbuf(k + 1)};
+  }
+  template <int BLK, bool FUSE, int GEO, bool ANY, int P16 = 0>
+  void pass_launch(const Depth& d, const HybridGeo& geo) {
+    hipLaunchKernelGGL((k_tile_pass<BITS, BLK, ITEMS, K, V, FUSE, Op, Op, GEO, ANY, P16>), dim3(d.rows), dim3(BLK), 0,
+                       st, d.src, d.dst, d.vsrc, d.vdst, (uint32_t)n, d.op, d.op_next, d.C, ws.tb, segbase, d.Cn, geo);
+  }
+
+  // The plan, the workspace, the sampler (reserved depth 0) or the counters'
+  // reset, the pieces' tile table.  *go stays false: not served (the LSD sort).
+  hipError_t setup(bool* go) {
+    DEPTHS = pc ? pc->depths : 16 / BITS;
+    nseg0 = pc ? pc->nseg : 1u;
+    const uint64_t NB64 = (uint64_t)nseg0 << (BITS * DEPTHS);
+    if (DEPTHS < 1 || NB64 > (1ull << 22) || (pc && (const void*)in == (const void*)out)) return hipErrorInvalidValue;
+    NB = (uint32_t)NB64;
+    lbits = (uint32_t)(W - BITS * DEPTHS);
+    fill = pc ? pc->fill : range_fill(span, W);
+    // libsortSetBucketMode(0) / LIBSORT_BUCKET_COUNT=0 keeps the LSD steps
+    cnt = kCntOk && get_bucket_mode() == 1 && W - BITS * DEPTHS <= 16;
+    bp = bucket_plan(n, NB, fill, (int)sizeof(K), cnt, LIBSORT_BUCKET64_BLOCK, kRetryBlock);
+    if (!bp.served) return hipSuccess;
+    T0 = pc ? pc->tiles : (uint32_t)((n + TILE0 - 1) / TILE0);
+    Tt = pc ? pc->tiles : (uint32_t)((n + TILE - 1) / TILE);
+    // reserved depth 0 (32-bit keys only, in != out: the fallback re-reads in):
+    // no count pass; depth 0 writes slices of ws.rsv (tile rows of depth 1
+    // numbered by slice capacity, at most tb1)
+    // (pieces: slices per (segment, digit, range), at most kRsvMaxSlices)
+    rnc = (pc ? nseg0 : 1u) * (uint32_t)RADIX;
+    rns = rnc * kRsvRanges;
+    int rmode = kCntOk && DEPTHS > 1 && (const void*)in != (const void*)out && (!pc || (pc->cum && rns <= kRsvMaxSlices))
+                    ? rsv_mode()
+                    : 0;
+    const int rper = rsv_pc_per(rnc);
+    const size_t rbound = pc ? rsv_capacity_bound_nc(n, rnc, kRsvBlocks * 256 * rper, TILE)
+                             : rsv_capacity_bound(n, BITS);
+    tb1 = (uint32_t)((rbound + TILE - 1) / TILE) + rns;
+    // the cursors after the slices, 256-byte aligned (8-bit: 64-bit adds)
+    rcur_off = (rbound + 63) & ~(size_t)63;
+    // The slices (~1.14 n words at 4-bit digits, ~1.28 n at 8-bit) stay cached
+    // in the workspace like its other buffers (grow-only, freed by
+    // libsortRelease).  If they cannot be allocated, depth 0 takes the count
+    // pass instead: the sort needs no more memory than before.
+    // (LIBSORT_HYB_RESERVE=nomem: as if the allocation failed -- tests)
+    if (rmode == 3 || (rmode && ws.ensure_rsv(rcur_off + (size_t)rns * kRsvCurStride) != hipSuccess)) {
+      (void)hipGetLastError();
+      rmode = 0;
     }
+    rsv = rmode != 0;
+    // pack16: after the last digit pass of a full-width
+    // sort every key sits in the bucket of its top 16 bits and the bucket index
+    // is that prefix, so the last pass writes only the low 16 bits (2 B per key
+    // instead of 4; element i = out's element i) and the bucket kernels read
+    // them back: 36 instead of 40 B per key and sort.
+    p16 = (kP16Ok && pack16_eligible(pc != nullptr, W, lbits, cnt, rmode)) ? pack16_mode() : 0;
+    p16buf = !p16 ? nullptr : reinterpret_cast<uint16_t*>(at(pack16_buf(DEPTHS)));
+    // 24-bit pieces are read by the reserved depth 0 only: otherwise the
+    // caller's gather (which unpacks them) and LSD sort
+    if (pc && pc->i8 && !rsv) return hipSuccess;
+    uint32_t TB = 0;
+    for (int k = 0; k < DEPTHS; ++k) TB = std::max(TB, tbound(k));
+    LS_TRY(ws.ensure_tiles((size_t)TB * RADIX, ((size_t)tp_chunks(TB, BITS) + 1) * RADIX));
+    const HybLayout L = hyb_layout(TB, NB, rnc);
+    LS_TRY(ws.ensure_hybrid(L.words));
+    uint32_t* const h = ws.hyb;
+    for (int i = 0; i < 2; ++i) {
+      tiles[i] = reinterpret_cast<uint4*>(h + L.tiles[i]);
+      cstart[i] = h + L.cstart[i];
+      ctile0[i] = h + L.ctile0[i];
+    }
+    segbase = h + L.segbase, nsize = h + L.nsize, ntl = h + L.ntl, ctr = h + L.ctr;
+    olist = h + L.olist, flist = h + L.flist, flist2 = h + L.flist2;
+    rpart = h + L.rpart, rslice = h + L.rslice;
+    rcur = rsv ? ws.rsv + rcur_off : nullptr;  // kRsvCurStride apart
+    uint32_t* Cn0 = ws.tc[1];  // depth 1's count rows (the fused counts of depth 0)
+    if (!rsv) {  // (reserved depth 0: k_rsv_sample sets them)
+      hipLaunchKernelGGL(k_hyb_init, dim3(1), dim3(64), 0, st, ctr, NB);  // one launch, not two memsets (4 fills)
+      LS_TRY(hipGetLastError());
+    } else {
+      // Reserved depth 0: sample -> slices (the depth-0 pass reserves its runs
+      // in them; the next depth's tiles and child starts from the cursors)
+      const Op op0 = make_digit<Op>((uint32_t)(W - BITS), (uint32_t)RADIX - 1u, bias);
+      ScopedTimer tm("rsvsample", st, n);
+      rseq = ++ws.hyb_seq;
+      if (pc) {
+        auto smp = rper == 4 ? k_rsv_sample_pc<RADIX, TILE, 4, Op>
+                   : rper == 8 ? k_rsv_sample_pc<RADIX, TILE, 8, Op> : k_rsv_sample_pc<RADIX, TILE, 16, Op>;
+        hipLaunchKernelGGL(smp, dim3(kRsvRanges * kRsvBlocks), dim3(256), 0, st,
+                           reinterpret_cast<const uint32_t*>(in), pc->i8, reinterpret_cast<const uint4*>(pc->dev), pc->cum,
+                           pc->np, nseg0, T0, (uint32_t)n, op0, rpart, rslice, rcur, ws.hyb_host, Cn0,
+                           BITS == 4 ? tb1 * (uint32_t)RADIX : 0u, ws.tticket + 32, ctr, NB, rmode == 2, rseq);
+      } else {
+        hipLaunchKernelGGL((k_rsv_sample<RADIX, TILE, Op>), dim3(kRsvRanges * kRsvBlocks), dim3(256), 0, st,
+                           reinterpret_cast<const uint32_t*>(in), (uint32_t)n, T0, op0, rpart, rslice, rcur,
+                           ws.hyb_host, Cn0, BITS == 4 ? tb1 * (uint32_t)RADIX : 0u, ws.tticket + 32, ctr, NB,
+                           rmode == 2, rseq);
+      }
+      LS_TRY(hipGetLastError());
+    }
+    if (pc) {
+      // depth 0's tile table and parent arrays from the piece table
+      const uint32_t g = std::max(T0, pc->nseg + 1);
+      hipLaunchKernelGGL((k_hyb_pieces<TILE>), dim3((g + 255) / 256), dim3(256), 0, st,
+                         reinterpret_cast<const uint4*>(pc->dev), pc->np, pc->dev + 4 * (size_t)pc->np, pc->nseg, T0,
+                         tiles[0], ctile0[0], cstart[0], ctr);
+      LS_TRY(hipGetLastError());
+    }
+    dstream = BITS == 8 && dstream_on() && (sizeof(K) == 8 || (kCntOk && !pc && dstream_u32_on()));
+    // (reserved depth 0: the stream in the slices' coordinates)
+    if (dstream) LS_TRY(ws.ensure_dstream(rsv ? std::max(n, rcur_off) : n));
+    ws.part_pending.valid = false;
+    *go = true;
+    return hipSuccess;
+  }
+
+  // Reserved depth 0 (sampled in setup): the pass reserves its runs in the
+  // slices; the next depth's tiles and child starts from the cursors.
+  // *go = false: skewed, the caller's LSD sort.
+  hipError_t reserved_depth0(bool* go) {
+    *go = false;
+    if constexpr (kCntOk) {
+      const Depth d = depth(0);
+      HybridGeo g0{tiles[0], ctr, nullptr, nullptr, nullptr, rcur, rslice, ctr + kCtrRsvOver, rns};
+      if (dstream && !d.last) g0.dout = ws.dstream;  // (the next depth's digits, slice positions)
+      if (pc) {
+        g0.i16 = pc->i16;
+        g0.i8 = pc->i8;
+        g0.seghi = pc->seghi;
+      }
+      {
+        ScopedTimer tm("tilepass", st, n);
+        if (pc)
+          pass_launch<B, BITS == 4, 5, true>(d, g0);
+        else
+          pass_launch<B, BITS == 4, 4, true>(d, g0);
+        LS_TRY(hipGetLastError());
+      }
+      {
+        ScopedTimer tm("hybplan", st, d.m);
+        hipLaunchKernelGGL((k_rsv_tiles<RADIX, TILE, BITS == 4>), dim3((tb1 + 255) / 256), dim3(256), 0, st, rslice,
+                           rcur, ctr + kCtrRsvOver, tb1, tiles[1], cstart[1], ctile0[1], ctr + kCtrTiles + 1, d.Cn,
+                           rnc);
+        LS_TRY(hipGetLastError());
+      }
+      // skew check on the sampled digit (pieces: child) sizes (the pass
+      // keeps the GPU busy; it wrote only ws.rsv, so abandoning leaves in
+      // intact).  The sampler raised its sequence word in the pinned
+      // mirror after the sizes: polled, not an event (an event record
+      // stalls the stream ~6 us).
+      LS_TRY(wait_host_word(ws.hyb_host + kHybSeqWord, rseq, st));
+      const uint32_t* sizes = ws.hyb_host + kHostDigits;
+      if (pc)
+        *go = !piece_child_skewed(sizes[0], BITS * (DEPTHS - 1), bp.cap);
+      else
+        *go = !top_digit_skewed(*std::max_element(sizes, sizes + RADIX), n, RADIX, fill, NB, bp.cap);
+    }
+    return hipSuccess;
+  }
+
+  // Depth k by its counts: count, column scan, the children's tiles and starts,
+  // the pass.  *go = false: skewed (seen after depth 0), the caller's LSD sort.
+  hipError_t table_depth(int k, bool* go) {
+    *go = false;
+    const Depth d = depth(k);
     // counts of this depth: depth 0 reads the keys (pieces: tile by tile from
     // the table); 4-bit deeper depths were counted by the previous pass
     // (fused); 8-bit deeper depths read the keys tile by tile from the table
     if (k == 0 && !pc) {
-      LS_TRY((tiles_counts<BITS, K, Op, V>(ws, src, n, op, T0, C, BITS == 4 ? Cn : nullptr,
+      LS_TRY((tiles_counts<BITS, K, Op, V>(ws, d.src, n, d.op, T0, d.C, BITS == 4 ? d.Cn : nullptr,
                                            BITS == 4 ? T0 * (uint32_t)RADIX : 0u, st)));
     } else if (BITS == 8 && dstream && k > 0) {
       // the digits depth k - 1 wrote (1 B per key)
-      LS_TRY((tiles_counts_u8<K, V, true, B>(ws, n, rows, C, tiles[k & 1], ctr + k, st)));
+      LS_TRY((tiles_counts_u8<K, V, true, B>(ws, n, d.rows, d.C, tiles[k & 1], ctr + kCtrTiles + k, st)));
     } else if (BITS == 8 || k == 0) {
       ScopedTimer tm("tilecounts", st, n);
-      hipLaunchKernelGGL((k_tile_counts<BITS, B, ITEMS, K, Op, true>), dim3(rows), dim3(B), 0, st, src,
-                         (uint32_t)n, op, C, nullptr, 0u, tiles[k & 1], ctr + k);
+      hipLaunchKernelGGL((k_tile_counts<BITS, B, ITEMS, K, Op, true>), dim3(d.rows), dim3(B), 0, st, d.src,
+                         (uint32_t)n, d.op, d.C, nullptr, 0u, tiles[k & 1], ctr + kCtrTiles + k);
       LS_TRY(hipGetLastError());
     }
-    LS_TRY(tiles_colscan<BITS>(ws, C, rows, st));
-    const uint32_t* D = tiles_digit_starts(ws, rows, BITS);
+    LS_TRY(tiles_colscan<BITS>(ws, d.C, d.rows, st));
+    const uint32_t* D = tiles_digit_starts(ws, d.rows, BITS);
     if (k == 0 && !pc) {
-      // the top digit's sizes, for the skew check below
-      LS_TRY(hipMemcpyAsync(ws.hyb_host, D, RADIX * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      // the top digit's starts, for the skew check below
+      LS_TRY(hipMemcpyAsync(ws.hyb_host + kHostDigits, D, RADIX * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
       LS_TRY(hipEventRecord(ws.hyb_evt, st));
     }
     {
-      ScopedTimer tm("hybplan", st, m);
-      // stats: the last depth's bucket sizes (ctr[11], [12]); pieces, depth 0
-      // of several: its largest child (ctr[13]) for the skew check
-      // (the last depth: ctr[11..14] -> hyb_host[256..259], written by the
-      // kernel's last block and read back while the last pass runs; other
+      ScopedTimer tm("hybplan", st, d.m);
+      // stats: the last depth's bucket sizes (ctr[kCtrMaxBucket], [kCtrPlanOver1]);
+      // pieces, depth 0 of several: its largest child (ctr[kCtrMaxChild]) for
+      // the skew check
+      // (the last depth: ctr[kCtrStats..] -> hyb_host[kHostStats..], written by
+      // the kernel's last block and read back while the last pass runs; other
       // depths: the next depth's tile prefix in the last block)
-      uint32_t* stats = last ? ctr + 11 : (pc && k == 0) ? ctr + 13 : nullptr;
-      hipLaunchKernelGGL((k_hyb_children<RADIX, TILE>), dim3((m + 255) / 256), dim3(256), 0, st, C, ws.tb, D, rows,
-                         (uint32_t)n, nseg, tab ? ctile0[k & 1] : nullptr, cstart[k & 1], T0, segbase,
-                         cstart[(k + 1) & 1], nsize, last ? nullptr : ntl, stats, cap1, ws.tticket + 48,
-                         last ? nullptr : ctile0[(k + 1) & 1], ctr + k + 1, ctr + 11,
-                         last ? ws.hyb_host + 256 : nullptr, ws.hyb_host + kHybSeqWord2, last ? ++ws.hyb_seq : 0u);
+      uint32_t* stats = d.last ? ctr + kCtrStats : (pc && k == 0) ? ctr + kCtrMaxChild : nullptr;
+      hipLaunchKernelGGL((k_hyb_children<RADIX, TILE>), dim3((d.m + 255) / 256), dim3(256), 0, st, d.C, ws.tb, D,
+                         d.rows, (uint32_t)n, d.nseg, d.tab ? ctile0[k & 1] : nullptr, cstart[k & 1], T0, segbase,
+                         cstart[(k + 1) & 1], nsize, d.last ? nullptr : ntl, stats, bp.cap1, ws.tticket + 48,
+                         d.last ? nullptr : ctile0[(k + 1) & 1], ctr + kCtrTiles + k + 1, ctr + kCtrStats,
+                         d.last ? ws.hyb_host + kHostStats : nullptr, ws.hyb_host + kHybSeqWord2,
+                         d.last ? ++ws.hyb_seq : 0u);
       LS_TRY(hipGetLastError());
-      if (last) {
+      if (d.last) {
         sseq = ws.hyb_seq;
       } else if (pc && k == 0) {
-        LS_TRY(hipMemcpyAsync(ws.hyb_host + 260, ctr + 13, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        LS_TRY(hipMemcpyAsync(ws.hyb_host + kHostMaxChild, ctr + kCtrMaxChild, sizeof(uint32_t), hipMemcpyDeviceToHost,
+                              st));
         LS_TRY(hipEventRecord(ws.hyb_evt, st));
       }
-      if (!last) {
+      if (!d.last) {
         const uint32_t nb_ = tbound(k + 1);
         hipLaunchKernelGGL((k_hyb_expand<RADIX, TILE>), dim3((nb_ + 255) / 256), dim3(256), 0, st,
-                           ctile0[(k + 1) & 1], m, cstart[(k + 1) & 1], nsize, ctr + k + 1, nb_,
-                           tiles[(k + 1) & 1], BITS == 4 ? Cn : nullptr);
+                           ctile0[(k + 1) & 1], d.m, cstart[(k + 1) & 1], nsize, ctr + kCtrTiles + k + 1, nb_,
+                           tiles[(k + 1) & 1], BITS == 4 ? d.Cn : nullptr);
         LS_TRY(hipGetLastError());
       }
     }
-    HybridGeo geo{tiles[k & 1], ctr + k, cstart[(k + 1) & 1], ctile0[(k + 1) & 1], nullptr, nullptr, nullptr, nullptr, 0u};
-    if (BITS == 8 && dstream && !last) geo.dout = ws.dstream;  // the next depth's digits
-    if (last && p16) {
+    HybridGeo geo{tiles[k & 1], ctr + kCtrTiles + k, cstart[(k + 1) & 1], ctile0[(k + 1) & 1], nullptr, nullptr,
+                  nullptr, nullptr, 0u};
+    if (BITS == 8 && dstream && !d.last) geo.dout = ws.dstream;  // the next depth's digits
+    if (d.last && p16) {
       // (the registry's sign that the packed last pass ran; no launch)
       ScopedTimer mark("pack16", st, n);
     }
     {
       ScopedTimer tm("tilepass", st, n);
-      if (last && p16) {
+      if (d.last && p16) {
         if constexpr (kP16Ok) {
           geo.o16 = p16buf;
-#if LIBSORT_PACK16_PAIRED_AB
-          if (p16 == 2)
-            hipLaunchKernelGGL((k_tile_pass<BITS, B, ITEMS, K, V, false, Op, Op, 1, true, 2>), dim3(rows), dim3(B), 0,
-                               st, src, dst, vsrc, vdst, (uint32_t)n, op, op_next, C, ws.tb, segbase, Cn, geo);
-          else
-#endif
-            hipLaunchKernelGGL((k_tile_pass<BITS, B, ITEMS, K, V, false, Op, Op, 1, true, 1>), dim3(rows), dim3(B), 0,
-                               st, src, dst, vsrc, vdst, (uint32_t)n, op, op_next, C, ws.tb, segbase, Cn, geo);
+          pass_launch<B, false, 1, true, 1>(d, geo);
         }
-      } else if (BITS == 4 && !last) {
-        if (!tab)
-          hipLaunchKernelGGL((k_tile_pass<BITS, B0, ITEMS, K, V, BITS == 4, Op, Op, 2, kAnyOrder>),
-                             dim3(rows), dim3(B0), 0, st, src, dst, vsrc, vdst, (uint32_t)n, op, op_next, C,
-                             ws.tb, segbase, Cn, geo);
+      } else if (BITS == 4 && !d.last) {
+        if (!d.tab)
+          pass_launch<B0, BITS == 4, 2, kAnyOrder>(d, geo);
         else
-          hipLaunchKernelGGL((k_tile_pass<BITS, B, ITEMS, K, V, BITS == 4, Op, Op, 3, kAnyOrder>),
-                             dim3(rows), dim3(B), 0, st, src, dst, vsrc, vdst, (uint32_t)n, op, op_next, C,
-                             ws.tb, segbase, Cn, geo);
-      } else if (!tab) {
-        hipLaunchKernelGGL((k_tile_pass<BITS, B0, ITEMS, K, V, false, Op, Op, 0, kAnyOrder>), dim3(rows),
-                           dim3(B0), 0, st, src, dst, vsrc, vdst, (uint32_t)n, op, op_next, C, ws.tb, segbase,
-                           Cn, geo);
+          pass_launch<B, BITS == 4, 3, kAnyOrder>(d, geo);
+      } else if (!d.tab) {
+        pass_launch<B0, false, 0, kAnyOrder>(d, geo);
       } else {
-        hipLaunchKernelGGL((k_tile_pass<BITS, B, ITEMS, K, V, false, Op, Op, 1, kAnyOrder>), dim3(rows),
-                           dim3(B), 0, st, src, dst, vsrc, vdst, (uint32_t)n, op, op_next, C, ws.tb, segbase,
-                           Cn, geo);
+        pass_launch<B, false, 1, kAnyOrder>(d, geo);
       }
       LS_TRY(hipGetLastError());
     }
+    *go = true;
     if (k == 0 && !pc) {
       // skew check (the pass above keeps the GPU busy meanwhile; it wrote
       // only tmp, so abandoning here leaves in intact)
       LS_TRY(hipEventSynchronize(ws.hyb_evt));
+      const uint32_t* starts = ws.hyb_host + kHostDigits;
       uint32_t mx = 0;
-      for (int d = 0; d < RADIX; ++d) {
-        const uint32_t e = d + 1 < RADIX ? ws.hyb_host[d + 1] : (uint32_t)n;
-        mx = std::max(mx, e - ws.hyb_host[d]);
+      for (int dg = 0; dg < RADIX; ++dg) {
+        const uint32_t e = dg + 1 < RADIX ? starts[dg + 1] : (uint32_t)n;
+        mx = std::max(mx, e - starts[dg]);
       }
-      // a top digit well above its share (beyond sampling noise), or one
-      // whose buckets would average > 0.9 of a block: the LSD sort instead
-      const double share = (double)n / (RADIX * fill);
-      if ((double)mx > 1.25 * share + 4.0 * std::sqrt(share) + 32.0 ||
-          (double)mx / (double)(NB / RADIX) > 0.9 * cap)
-        return hipSuccess;
-    } else if (k == 0 && !last) {
-      // pieces: a depth-0 child whose buckets would average > 0.9 of a block
-      // (a skewed input): the caller's LSD sort instead (in is untouched)
+      *go = !top_digit_skewed(mx, n, RADIX, fill, NB, bp.cap);
+    } else if (k == 0 && !d.last) {
+      // pieces: a skewed input, the caller's LSD sort instead (in is untouched)
       LS_TRY(hipEventSynchronize(ws.hyb_evt));
-      if ((double)ws.hyb_host[260] / (double)(1ull << (BITS * (DEPTHS - 1))) > 0.9 * cap) return hipSuccess;
+      *go = !piece_child_skewed(ws.hyb_host[kHostMaxChild], BITS * (DEPTHS - 1), bp.cap);
+    }
+    return hipSuccess;
+  }
+
+  // ---- bucket phase: the NB buckets sorted in place in out ----
+  // per launch: grid, the bucket count (device) and its cap, the list the blocks
+  // read (null: every bucket), the count and list of the buckets over the block
+  struct SizeArgs {
+    uint32_t grid;
+    const uint32_t* nbp;
+    uint32_t capn;
+    const uint32_t* il;
+    uint32_t *ov, *ol;
+  };
+
+  // the counting placement (packed: from the u16 array)
+  template <int BLK, int I, int MODE>
+  void count_launch(const SizeArgs& a) {
+    auto go = [&](auto packed) {
+      constexpr bool P = decltype(packed)::value;
+      hipLaunchKernelGGL((k_bucket_count<BLK, I, Op, MODE, false, P>), dim3(a.grid), dim3(BLK), 0, st,
+                         reinterpret_cast<const uint32_t*>(P ? (const void*)p16buf : (const void*)out),
+                         reinterpret_cast<uint32_t*>(out), bstart, nsize, a.nbp, a.capn, a.il, lbits, bias, a.ov, a.ol,
+                         a.ol == flist ? NB : kListCap, lsd_n, lsd_l, rty_n, rty_l);
+    };
+    if constexpr (kP16Ok && (MODE == kCnt3F || MODE == kCnt2F)) {
+      if (p16) return go(std::true_type{});
+    }
+    go(std::false_type{});
+  }
+
+  // One size's blocks of BLK x I slots.  C: the counting placement (32-bit
+  // keys without values, lbits <= 16; the 2-bit cells only in the first size
+  // of 256-thread blocks); else (u64 key, u32 payload) pairs by k_bucket_pairs
+  // or the LSD steps of k_bucket_sort.
+  template <bool C, int BLK, int I, bool FIRST>
+  void size_launch(const SizeArgs& a) {
+    if constexpr (C) {
+      switch (lbits <= 12 ? kCntSmall : lbits != 16 ? kCnt3 : two ? kCnt2F : kCnt3F) {
+        case kCntSmall: count_launch<BLK, I, kCntSmall>(a); break;
+        case kCnt3: count_launch<BLK, I, kCnt3>(a); break;
+        case kCnt3F: count_launch<BLK, I, kCnt3F>(a); break;
+        default:
+          if constexpr (BLK == 256 && FIRST) count_launch<BLK, I, kCnt2F>(a);
+          break;
+      }
+    } else {
+      if constexpr (kPairCnt) {
+        if (pcnt) {
+          // the counting placement, 1024-thread blocks of at least the slots asked for
+          constexpr int PI = std::max(4, (BLK * I + 1023) / 1024);
+          hipLaunchKernelGGL((k_bucket_pairs<1024, PI, Op>), dim3(a.grid), dim3(1024), 0, st,
+                             reinterpret_cast<const uint64_t*>(out), reinterpret_cast<uint64_t*>(out),
+                             reinterpret_cast<const uint32_t*>(vout), reinterpret_cast<uint32_t*>(vout), bstart, nsize,
+                             a.nbp, a.capn, a.il, lbits, (uint64_t)bias, a.ov, a.ol, kListCap, ctr + kCtrOvfN, flist);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((k_bucket_sort<BITS, BLK, I, Op, K, V, FIXB>), dim3(a.grid), dim3(BLK), 0, st, out, out, vout,
+                         vout, bstart, nsize, a.nbp, a.capn, a.il, lbits, bias, a.ov, a.ol, kListCap);
     }
   }
+
+  // The first size over every bucket, then the second over the buckets it
+  // listed (n2 of them as planned; none: no launch).  2-bit cells: one launch,
+  // the buckets over the first size join the retry list.
+  template <bool C, int CLS>
+  hipError_t sizes_launch() {
+    constexpr int BLK = class_block(CLS, BB), I1 = class_items1(CLS, BB), I2 = class_items2(CLS, BB);
+    size_launch<C, BLK, I1, true>(
+        {NB, ctr + kCtrBuckets, NB, nullptr, two ? ctr + kCtrOvfN : ctr + kCtrOver1, two ? flist : olist});
+    LS_TRY(hipGetLastError());
+    if (n2 && !two) size_launch<C, BLK, I2, false>({n2, ctr + kCtrOver1, kListCap, olist, ctr + kCtrOver2, nullptr});
+    return hipGetLastError();
+  }
+
+  // The listed buckets, persistent grids over the lists (none listed: the
+  // blocks read the count and exit).  Counting placement: the 3-bit retry of
+  // the 2-bit cells' list (rty_l -> flist2 for what overflows again), then the
+  // LSD steps over lsd_l in blocks of the second size (3-bit overflow: 8+
+  // equal keys); packed: both read the (untouched) u16 array.  Pairs: those
+  // whose 3-bit counts would wrap (8+ equal x; their length <= cap, the
+  // planning's bound), the LSD steps + fix-up over flist.
+  template <bool C, int CLS>
+  hipError_t lists_launch() {
+    constexpr int BLK = class_block(CLS, BB), I2 = class_items2(CLS, BB);
+    const uint32_t cus = (uint32_t)std::max(1, ws.num_cus);
+    if constexpr (C) {
+      auto go = [&](auto packed) -> hipError_t {
+        constexpr bool P = decltype(packed)::value;
+        const uint32_t* const ci =
+            P ? reinterpret_cast<const uint32_t*>(p16buf) : reinterpret_cast<const uint32_t*>(out);
+        if constexpr (kBucketClass[CLS].block == 256) {
+          if (two) {
+            constexpr int RI = class_retry_items(CLS, kRetryBlock);
+            hipLaunchKernelGGL((k_bucket_count<kRetryBlock, RI, Op, kCnt3F, true, P>),
+                               dim3(std::min<uint32_t>(NB, cus * 5)), dim3(kRetryBlock), 0, st, ci,
+                               reinterpret_cast<uint32_t*>(out), bstart, nsize, ctr + kCtrOvfN, NB, flist, lbits, bias,
+                               ctr + kCtrOver2, nullptr, 0u, ctr + kCtrLsdN2, flist2, nullptr, nullptr);
+            LS_TRY(hipGetLastError());
+          }
+        }
+        // (packed, duplicate-heavy keys list every bucket here: three
+        // 256-thread blocks per CU, what its ~130 VGPRs hold at once, not two,
+        // so the packed sort keeps within 3x of the uniform one, which pack16
+        // made faster)
+        const uint32_t per_cu = P && BLK == 256 ? 3u : 2u;
+        hipLaunchKernelGGL((k_bucket_sort<BITS, BLK, I2, Op, K, V, 0, true, P>), dim3(std::min<uint32_t>(NB, cus * per_cu)),
+                           dim3(BLK), 0, st, reinterpret_cast<const K*>(ci), out, vout, vout, bstart, nsize, lsd_n, NB,
+                           lsd_l, lbits, bias, ctr + kCtrRsvOver, nullptr, 0u);
+        return hipGetLastError();
+      };
+      if constexpr (kP16Ok) {
+        if (p16) return go(std::true_type{});
+      }
+      return go(std::false_type{});
+    } else if constexpr (kPairCnt) {
+      if (pcnt)
+        hipLaunchKernelGGL((k_bucket_sort<BITS, BLK, I2, Op, K, V, FIXB, true>), dim3(std::min<uint32_t>(NB, cus * 2)),
+                           dim3(BLK), 0, st, out, out, vout, vout, bstart, nsize, ctr + kCtrOvfN, NB, flist, lbits,
+                           bias, ctr + kCtrRsvOver, nullptr, 0u);
+    }
+    return hipGetLastError();
+  }
+
+  template <bool C, int CLS>
+  hipError_t class_launch() {
+    LS_TRY((sizes_launch<C, CLS>()));
+    return lists_launch<C, CLS>();
+  }
+  template <bool C>
+  hipError_t classes_launch() {
+    switch (bp.cls) {
+      case 0: return class_launch<C, 0>();
+      case 1: return class_launch<C, 1>();
+      case 2: return class_launch<C, 2>();
+      case 3: return class_launch<C, 3>();
+      case 4:
+        if constexpr (sizeof(K) == 4) return class_launch<C, 4>();
+        break;
+      default:
+        if constexpr (C) return class_launch<C, 5>();
+        break;
+    }
+    return hipSuccess;
+  }
+
+  // Bucket sort of the NB buckets in place in out (cstart / nsize of the last
+  // depth's children)
+  hipError_t bucket_phase() {
+    ScopedTimer tm("bucketsort", st, n);
+    bstart = cstart[DEPTHS & 1];
+    // the second size's grid: the buckets over the first block, as planned
+    // (k_hyb_children's count, the same cap as the first launch lists by)
+    n2 = std::min<uint32_t>(ws.hyb_host[kHostPlanOver1], kListCap);
+    // 2-bit cells (256-thread blocks, lbits 16): their lightly overflowed
+    // buckets (a value with 4+ keys; ~4% of uniform 4096-key buckets) and
+    // the buckets over the first block get a 3-bit retry in blocks of the
+    // second size (a persistent LIST launch over flist, count
+    // ctr[kCtrOvfN]: no separate second-size launch); heavy overflows, and
+    // the retry's, go to the LSD steps (flist2, count ctr[kCtrLsdN2]); other
+    // modes list straight for the LSD steps (flist)
+    two = cnt && lbits == 16 && BB == 256 && bp.cls <= 3 && bucket2_on();
+    // (u64 key, u32 payload) pairs: k_bucket_pairs (LIBSORT_PAIR_COUNT=0:
+    // the LSD steps + fix-up of k_bucket_sort FIX)
+    pcnt = kPairCnt && lbits >= 16 && lbits <= 48 && pair_count_on();
+    lsd_n = two ? ctr + kCtrLsdN2 : ctr + kCtrOvfN, lsd_l = two ? flist2 : flist;  // the LSD steps' list
+    rty_n = two ? ctr + kCtrOvfN : nullptr, rty_l = two ? flist : nullptr;        // the 3-bit retry's
+    if constexpr (kCntOk) {
+      if (cnt) return classes_launch<true>();
+    }
+    return classes_launch<false>();
+  }
+};
+
+template <int BITS, typename Op, typename K = uint32_t, typename V = NoValue>
+hipError_t sort_hybrid(Workspace& ws, const K* in, K* out, K* tmp, const V* vin, V* vout, V* vtmp, size_t n, int W,
+                       uint32_t bias, hipStream_t st, bool* handled, uint64_t span = 0,
+                       const HybPieces* pc = nullptr) {
+  *handled = false;
+  HybridSort<BITS, Op, K, V> h{ws, in, out, tmp, vin, vout, vtmp, n, W, bias, st, span, pc};
+  bool go = false;
+  LS_TRY(h.setup(&go));
+  for (int k = 0; go && k < h.DEPTHS; ++k) LS_TRY(k == 0 && h.rsv ? h.reserved_depth0(&go) : h.table_depth(k, &go));
+  if (!go) return hipSuccess;
   // the bucket sizes (read back while the last pass runs): a bucket larger
   // than the second block, or more buckets over the first than its list
   // holds -> the LSD sort of out (any order sorts) instead of the bucket sort
   // (polled: the children kernel raised the sequence word after them)
-  LS_TRY(wait_host_word(ws.hyb_host + kHybSeqWord2, sseq, st));
+  LS_TRY(wait_host_word(ws.hyb_host + kHybSeqWord2, h.sseq, st));
   // reserved depth 0 overflowed (a slice's sample undercounted it): the
   // later depths did nothing; the caller's LSD sort from the input instead
-  if (rsv && ws.hyb_host[259]) return hipSuccess;
+  if (h.rsv && ws.hyb_host[kHostRsvOver]) return hipSuccess;
   *handled = true;
-  if (ws.hyb_host[257] > kListCap || ws.hyb_host[256] > cap) {
-    if (p16) {
+  if (ws.hyb_host[kHostPlanOver1] > kListCap || ws.hyb_host[kHostMaxBucket] > h.bp.cap) {
+    if (h.p16) {
       // (the packed last pass is already queued: whole keys into out first)
       ScopedTimer tm("pack16expand", st, n);
-      hipLaunchKernelGGL(k_pack16_expand, dim3(std::min<uint32_t>(NB, 4096u), 8), dim3(256), 0, st, p16buf,
-                         reinterpret_cast<uint32_t*>(out), cstart[DEPTHS & 1], nsize, NB);
+      hipLaunchKernelGGL(k_pack16_expand, dim3(std::min<uint32_t>(h.NB, 4096u), 8), dim3(256), 0, st, h.p16buf,
+                         reinterpret_cast<uint32_t*>(out), h.cstart[h.DEPTHS & 1], h.nsize, h.NB);
       LS_TRY(hipGetLastError());
     }
     // pieces: every bit (the segments' own bits vary across out)
-    if (pc) return sort_impl<K, V>(ws, out, out, tmp, vout, vout, vtmp, n, 0, 8 * (int)sizeof(K), BITS, st);
-    return sort_impl<K, V>(ws, out, out, tmp, vout, vout, vtmp, n, 0, W, BITS, st, bias);
+    if (pc)
+      LS_TRY((sort_impl<K, V>(ws, out, out, tmp, vout, vout, vtmp, n, 0, 8 * (int)sizeof(K), BITS, st)));
+    else
+      LS_TRY((sort_impl<K, V>(ws, out, out, tmp, vout, vout, vtmp, n, 0, W, BITS, st, bias)));
+  } else {
+    LS_TRY(h.bucket_phase());
   }
-  // bucket sort of the NB buckets in place in out (cstart/nsize of the last
-  // depth's children)
-  {
-    ScopedTimer tm("bucketsort", st, n);
-    const uint32_t* bstart = cstart[DEPTHS & 1];
-    // 64-bit keys: 512-thread blocks (BB; the same slots in half the keys per
-    // thread: 152 -> ~90 VGPRs for (u64, u32) pairs at 17 slots per 256)
-    // 64-bit keys: on-chip steps over the top 16 of the 48 bucket bits, then
-    // the tie fix-up (k_bucket_sort FIX)
-    constexpr int FIXB = sizeof(K) == 8 ? LIBSORT_BUCKET64_FIX : 0;
-    constexpr bool kPairCnt = sizeof(K) == 8 && std::is_same<V, uint32_t>::value && FIXB > 0;
-    // the second size's grid: the buckets over the first block, as planned
-    // (k_hyb_children's count, the same cap as the first launch lists by);
-    // none: no launch
-    const uint32_t n2 = std::min<uint32_t>(ws.hyb_host[257], kListCap);
-    // 32-bit keys without values, lbits <= 16: the counting placement
-    // (k_bucket_sort CNT, `cnt` above)
-    auto launch = [&](auto cnt_c) -> hipError_t {
-      constexpr bool C = decltype(cnt_c)::value;
-      // 2-bit cells (256-thread blocks, lbits 16): their lightly overflowed
-      // buckets (a value with 4+ keys; ~4% of uniform 4096-key buckets) and
-      // the buckets over the first block get a 3-bit retry in blocks of the
-      // second size (a persistent LIST launch over flist, count ctr[15]: no
-      // separate second-size launch); heavy overflows, and the retry's, go
-      // to the LSD steps (flist2, count ctr[7]); other modes list straight
-      // for the LSD steps (flist)
-      const bool two = C && lbits == 16 && BB == 256 && cls <= 3 && bucket2_on();
-      // (u64 key, u32 payload) pairs: k_bucket_pairs (LIBSORT_PAIR_COUNT=0:
-      // the LSD steps + fix-up of k_bucket_sort FIX)
-      const bool pcnt = kPairCnt && lbits >= 16 && lbits <= 48 && pair_count_on();
-      // (inline: the retry list holds only the buckets over the first block,
-      // so the 3-bit LIST launch runs only when the planning counted any)
-      const bool inl = two && bucket2_inline_on();
-      uint32_t* const lsd_n = two ? ctr + 7 : ctr + 15;  // the LSD steps' list
-      uint32_t* const lsd_l = two ? flist2 : flist;
-      uint32_t* const rty_n = two ? ctr + 15 : nullptr;
-      uint32_t* const rty_l = two ? flist : nullptr;
-#if LIBSORT_BUCKET2_INLINE_AB
-#define LS_BS_INL(B, I, G, NBP, CAPN, IL, OV, OL)                                                            \
-  hipLaunchKernelGGL((k_bucket_count<B, (I), Op, kCnt2F, false, true>), dim3(G), dim3(B), 0, st, ci_, co_, \
-                     bstart, nsize, NBP, CAPN, IL, lbits, bias, OV, OL, ocap_, lsd_n, lsd_l, rty_n, rty_l)
-#else
-#define LS_BS_INL(B, I, G, NBP, CAPN, IL, OV, OL) (void)0
-#endif
-      // (lbits == 16: from the u16 array when the last pass was packed)
-#define LS_BC16(B, I, M, G, NBP, CAPN, IL, OV, OL)                                                               \
-  do {                                                                                                           \
-    if constexpr (kP16Ok) {                                                                                      \
-      if (p16) {                                                                                                 \
-        hipLaunchKernelGGL((k_bucket_count<B, (I), Op, M, false, false, true>), dim3(G), dim3(B), 0, st, ci_,    \
-                           co_, bstart, nsize, NBP, CAPN, IL, lbits, bias, OV, OL, ocap_, lsd_n, lsd_l, rty_n,   \
-                           rty_l);                                                                               \
-        break;                                                                                                   \
-      }                                                                                                          \
-    }                                                                                                            \
-    hipLaunchKernelGGL((k_bucket_count<B, (I), Op, M>), dim3(G), dim3(B), 0, st, ci_, co_, bstart, nsize, NBP,   \
-                       CAPN, IL, lbits, bias, OV, OL, ocap_, lsd_n, lsd_l, rty_n, rty_l);                        \
-  } while (0)
-#define LS_BSX(B, I, G, NBP, CAPN, IL, OV, OL)                                                                   \
-  if constexpr (C) {                                                                                             \
-    const uint32_t* ci_ = p16 ? reinterpret_cast<const uint32_t*>(p16buf) : reinterpret_cast<const uint32_t*>(out); \
-    uint32_t* co_ = reinterpret_cast<uint32_t*>(out);                                                            \
-    const uint32_t ocap_ = (OL) == flist ? NB : kListCap;                                                        \
-    if (lbits <= 12)                                                                                             \
-      hipLaunchKernelGGL((k_bucket_count<B, (I), Op, kCntSmall>), dim3(G), dim3(B), 0, st, ci_, co_, bstart,     \
-                         nsize, NBP, CAPN, IL, lbits, bias, OV, OL, ocap_, lsd_n, lsd_l, rty_n, rty_l);             \
-    else if (lbits != 16)                                                                                        \
-      hipLaunchKernelGGL((k_bucket_count<B, (I), Op, kCnt3>), dim3(G), dim3(B), 0, st, ci_, co_, bstart, nsize,  \
-                         NBP, CAPN, IL, lbits, bias, OV, OL, ocap_, lsd_n, lsd_l, rty_n, rty_l);                    \
-    else if (B == 256 && two && inl)                                                                             \
-      LS_BS_INL(B, I, G, NBP, CAPN, IL, OV, OL);                                                                 \
-    else if (B == 256 && two)                                                                                    \
-      LS_BC16(B, I, kCnt2F, G, NBP, CAPN, IL, OV, OL);                                                           \
-    else                                                                                                         \
-      LS_BC16(B, I, kCnt3F, G, NBP, CAPN, IL, OV, OL);                                                           \
-  } else if (pcnt) {                                                                                             \
-    if constexpr (kPairCnt) {                                                                                    \
-      /* (u64, u32) pairs: the counting placement, 1024-thread blocks of at least the slots asked for */         \
-      constexpr int PI_ = std::max(4, ((B) * (I) + 1023) / 1024);                                                \
-      hipLaunchKernelGGL((k_bucket_pairs<1024, PI_, Op>), dim3(G), dim3(1024), 0, st,                            \
-                         reinterpret_cast<const uint64_t*>(out), reinterpret_cast<uint64_t*>(out),               \
-                         reinterpret_cast<const uint32_t*>(vout), reinterpret_cast<uint32_t*>(vout), bstart,     \
-                         nsize, NBP, CAPN, IL, lbits, (uint64_t)bias, OV, OL, kListCap, ctr + 15, flist);        \
-    }                                                                                                            \
-  } else {                                                                                                       \
-    hipLaunchKernelGGL((k_bucket_sort<BITS, B, (I), Op, K, V, FIXB>), dim3(G), dim3(B), 0, st, out, out, vout, vout, \
-                       bstart, nsize, NBP, CAPN, IL, lbits, bias, OV, OL, kListCap);                             \
-  }
-#define LS_BS(I, G, NBP, CAPN, IL, OV, OL) LS_BSX(BB, ((I) * 256 + BB - 1) / BB, G, NBP, CAPN, IL, OV, OL)
-#define LS_BS2(I)                                                   \
-  if (two) {                                                        \
-    /* the buckets over the first block join the retry list */      \
-    LS_BS(I, NB, ctr + 9, NB, nullptr, ctr + 15, flist);            \
-  } else {                                                          \
-    LS_BS(I, NB, ctr + 9, NB, nullptr, ctr + 8, olist);             \
-    LS_TRY(hipGetLastError());                                      \
-    if (n2) {                                                       \
-      LS_BS(I + 6, n2, ctr + 8, kListCap, olist, ctr + 10, nullptr); \
-    }                                                               \
-  }
-#define LS_BS512(I, G, NBP, CAPN, IL, OV, OL) LS_BSX(512, I, G, NBP, CAPN, IL, OV, OL)
-#define LS_BS1024(I, G, NBP, CAPN, IL, OV, OL) LS_BSX(1024, I, G, NBP, CAPN, IL, OV, OL)
-      // the buckets the counting placement listed (3-bit overflow: 8+ equal
-      // keys), by the LSD steps in blocks of the second size: a persistent
-      // grid over the list (none listed: the blocks read the count and exit)
-#define LS_BSL(B, I)                                                                                               \
-  if constexpr (C) {                                                                                               \
-    constexpr int RI_ = ((I) * 256 + kRetryBlock - 1) / kRetryBlock;                                               \
-    const dim3 rg_(std::min<uint32_t>(NB, (uint32_t)std::max(1, ws.num_cus) * 5));                                 \
-    const dim3 lg_(std::min<uint32_t>(NB, (uint32_t)std::max(1, ws.num_cus) * 2));                                 \
-    bool packed_ = false;                                                                                          \
-    if constexpr (kP16Ok) {                                                                                        \
-      if (p16) {                                                                                                   \
-        /* both lists read the (untouched) u16 array */                                                            \
-        packed_ = true;                                                                                            \
-        if (two && (!inl || n2 > 0)) {                                                                             \
-          hipLaunchKernelGGL((k_bucket_count<kRetryBlock, RI_, Op, kCnt3F, true, false, true>), rg_,               \
-                             dim3(kRetryBlock), 0, st, reinterpret_cast<const uint32_t*>(p16buf),                  \
-                             reinterpret_cast<uint32_t*>(out), bstart, nsize, ctr + 15, NB, flist, lbits, bias,    \
-                             ctr + 10, nullptr, 0u, ctr + 7, flist2, nullptr, nullptr);                            \
-          LS_TRY(hipGetLastError());                                                                               \
-        }                                                                                                          \
-        /* (duplicate-heavy keys list every bucket here: three 256-thread blocks per CU, what its ~130 VGPRs    \
-           hold at once, not two, so the packed sort keeps within 3x of the uniform one, which pack16 made     \
-           faster) */                                                                                              \
-        const dim3 lg16_(std::min<uint32_t>(NB, (uint32_t)std::max(1, ws.num_cus) * ((B) == 256 ? 3u : 2u)));      \
-        hipLaunchKernelGGL((k_bucket_sort<BITS, B, (I), Op, K, V, 0, true, true>), lg16_, dim3(B), 0, st,          \
-                           reinterpret_cast<const K*>(p16buf), out, vout, vout, bstart, nsize, lsd_n, NB, lsd_l,   \
-                           lbits, bias, ctr + 14, nullptr, 0u);                                                    \
-        LS_TRY(hipGetLastError());                                                                                 \
-      }                                                                                                            \
-    }                                                                                                              \
-    if (!packed_) {                                                                                                \
-      if (two && (!inl || n2 > 0)) {                                                                               \
-        hipLaunchKernelGGL((k_bucket_count<kRetryBlock, RI_, Op, kCnt3F, true>), rg_, dim3(kRetryBlock), 0, st,    \
-                           reinterpret_cast<const uint32_t*>(out), reinterpret_cast<uint32_t*>(out), bstart,       \
-                           nsize, ctr + 15, NB, flist, lbits, bias, ctr + 10, nullptr, 0u, ctr + 7, flist2,        \
-                           nullptr, nullptr);                                                                      \
-        LS_TRY(hipGetLastError());                                                                                 \
-      }                                                                                                            \
-      hipLaunchKernelGGL((k_bucket_sort<BITS, B, (I), Op, K, V, 0, true>), lg_, dim3(B), 0, st, out, out, vout,    \
-                         vout, bstart, nsize, lsd_n, NB, lsd_l, lbits, bias, ctr + 14, nullptr, 0u);               \
-      LS_TRY(hipGetLastError());                                                                                   \
-    }                                                                                                              \
-  } else if constexpr (kPairCnt) {                                                                                 \
-    if (pcnt) {                                                                                                    \
-      /* the pairs whose 3-bit counts would wrap (8+ equal x; their length <= cap, the planning's bound):        \
-         the LSD steps + fix-up, persistent over flist */                                                          \
-      hipLaunchKernelGGL((k_bucket_sort<BITS, B, (I), Op, K, V, FIXB, true>),                                      \
-                         dim3(std::min<uint32_t>(NB, (uint32_t)std::max(1, ws.num_cus) * 2)), dim3(B), 0, st, out, \
-                         out, vout, vout, bstart, nsize, ctr + 15, NB, flist, lbits, bias, ctr + 14, nullptr, 0u);  \
-      LS_TRY(hipGetLastError());                                                                                   \
-    }                                                                                                              \
-  }
-      switch (cls) {
-        case 0: LS_BS2(9); LS_TRY(hipGetLastError()); LS_BSL(BB, (15 * 256 + BB - 1) / BB); break;
-        case 1: LS_BS2(13); LS_TRY(hipGetLastError()); LS_BSL(BB, (19 * 256 + BB - 1) / BB); break;
-        case 2: LS_BS2(17); LS_TRY(hipGetLastError()); LS_BSL(BB, (23 * 256 + BB - 1) / BB); break;
-        case 3: LS_BS2(19); LS_TRY(hipGetLastError()); LS_BSL(BB, (25 * 256 + BB - 1) / BB); break;
-        case 4:
-          if constexpr (sizeof(K) == 4) {
-            LS_BS512(17, NB, ctr + 9, NB, nullptr, ctr + 8, olist);
-            LS_TRY(hipGetLastError());
-            if (n2) {
-              LS_BS512(23, n2, ctr + 8, kListCap, olist, ctr + 10, nullptr);
-            }
-            LS_TRY(hipGetLastError());
-            LS_BSL(512, 23);
-          }
-          break;
-        default:
-          if constexpr (C) {
-            LS_BS1024(17, NB, ctr + 9, NB, nullptr, ctr + 8, olist);
-            LS_TRY(hipGetLastError());
-            if (n2) {
-              LS_BS1024(23, n2, ctr + 8, kListCap, olist, ctr + 10, nullptr);
-            }
-            LS_TRY(hipGetLastError());
-            LS_BSL(1024, 23);
-          }
-          break;
-      }
-      return hipGetLastError();
-    };
-    if constexpr (kCntOk) {
-      if (cnt)
-        LS_TRY(launch(std::true_type{}));
-      else
-        LS_TRY(launch(std::false_type{}));
-    } else {
-      LS_TRY(launch(std::false_type{}));
-    }
-#undef LS_BSL
-#undef LS_BSX
-#undef LS_BC16
-#undef LS_BS1024
-#undef LS_BS512
-#undef LS_BS2
-#undef LS_BS
-  }
+  ws.last_algo = 4;
   return hipSuccess;
+}
+
+// The hybrid by digit width, and for u32 keys alone by digit operator (biased:
+// range sorts of key - bias)
+template <typename Op, typename K, typename V>
+hipError_t sort_hybrid_bits(int digit_bits, Workspace& ws, const K* in, K* out, K* tmp, const V* vin, V* vout, V* vtmp,
+                            size_t n, int W, uint32_t bias, hipStream_t st, bool* handled, uint64_t span = 0,
+                            const HybPieces* pc = nullptr) {
+  if (digit_bits == 4) return sort_hybrid<4, Op, K, V>(ws, in, out, tmp, vin, vout, vtmp, n, W, bias, st, handled, span, pc);
+  return sort_hybrid<8, Op, K, V>(ws, in, out, tmp, vin, vout, vtmp, n, W, bias, st, handled, span, pc);
+}
+inline hipError_t sort_hybrid_u32(Workspace& ws, const uint32_t* in, uint32_t* out, uint32_t* tmp, size_t n, int W,
+                                  int digit_bits, uint32_t bias, hipStream_t st, bool* handled, uint64_t span,
+                                  const HybPieces* pc) {
+  NoValue* nv = nullptr;
+  if (bias) return sort_hybrid_bits<BiasedDigit>(digit_bits, ws, in, out, tmp, nv, nv, nv, n, W, bias, st, handled, span, pc);
+  return sort_hybrid_bits<RadixDigit>(digit_bits, ws, in, out, tmp, nv, nv, nv, n, W, 0u, st, handled, span, pc);
 }
 
 }  // namespace
@@ -5237,22 +5074,11 @@ hipError_t sort_u32(Workspace& ws, const uint32_t* in, uint32_t* out, uint32_t* 
   // sort, or a range sort (keys in [bias, bias + 2^hi)) of >= 20 bits
   const bool whole = !d_bounds && lo == 0 && ((hi == 32 && !bias) || (range && hi >= 20));
   if (whole && (digit_bits == 4 || digit_bits == 8) &&
-      ((hyb == 1 && n >= hyb_min_keys_u32(range && hi < 32) && n <= kHybMaxKeys) || (hyb == 2 && n >= 1024 && n <= kHybMaxKeys)) &&
+      hybrid_serves(hyb, n, hyb_min_keys_u32(range && hi < 32), kHybMaxKeys) &&
       (get_algorithm() == 0 || get_algorithm() == 3) && in != tmp) {
     bool handled = false;
-    NoValue* nv = nullptr;
-    if (bias && digit_bits == 4)
-      LS_TRY((sort_hybrid<4, BiasedDigit>(ws, in, out, tmp, nv, nv, nv, n, hi, bias, st, &handled, span)));
-    else if (bias)
-      LS_TRY((sort_hybrid<8, BiasedDigit>(ws, in, out, tmp, nv, nv, nv, n, hi, bias, st, &handled, span)));
-    else if (digit_bits == 4)
-      LS_TRY((sort_hybrid<4, RadixDigit>(ws, in, out, tmp, nv, nv, nv, n, hi, 0u, st, &handled, span)));
-    else
-      LS_TRY((sort_hybrid<8, RadixDigit>(ws, in, out, tmp, nv, nv, nv, n, hi, 0u, st, &handled, span)));
-    if (handled) {
-      ws.last_algo = 4;
-      return hipSuccess;
-    }
+    LS_TRY(sort_hybrid_u32(ws, in, out, tmp, n, hi, digit_bits, bias, st, &handled, span, nullptr));
+    if (handled) return hipSuccess;
   }
   LS_TRY((sort_impl<uint32_t, NoValue>(ws, in, out, tmp, nullptr, nullptr, nullptr, n, lo, hi,
                                       digit_bits, st, bias)));
@@ -5323,129 +5149,34 @@ hipError_t sort_pieces_impl(Workspace& ws, const uint32_t* in, const PlanarPiece
       bits > 32 || (digit_bits != 4 && digit_bits != 8) ||
       (planar && (bits != 24 || bias != 0 || !pl.i16 || pl.hi0 + nseg > 256u)))
     return hipErrorInvalidValue;
-  // the non-empty pieces, checked: segments non-decreasing and < nseg, offsets
-  // below 2^32, lengths summing to n
-  std::vector<size_t> keep;
-  keep.reserve(np);
-  uint64_t total = 0, maxlen = 0;
-  uint32_t prev = 0;
-  for (size_t p = 0; p < np; ++p) {
-    if (seg[p] < prev || seg[p] >= nseg) return hipErrorInvalidValue;
-    prev = seg[p];
-    if (!len[p]) continue;
-    if (off[p] + len[p] > 0xffffffffull) return hipErrorInvalidValue;
-    total += len[p];
-    maxlen = std::max(maxlen, len[p]);
-    keep.push_back(p);
-  }
-  if (total != n || keep.size() > 65535) return hipErrorInvalidValue;
-  const uint32_t K = (uint32_t)keep.size();
-  // segment sizes: the largest sets the digit passes, the populated ones the
-  // bucket blocks' size class (a round's last group may span many empty
-  // digits)
-  std::vector<uint64_t> segsize(nseg, 0);
-  for (size_t p : keep) segsize[seg[p]] += len[p];
-  uint64_t maxseg = 0;
-  uint32_t npop = 0;
-  // the populated segments only, renumbered in order (empty segments hold no
-  // keys, so the output order is unchanged; a round over many empty digits
-  // would otherwise launch a bucket block per empty bucket: 2^29 keys in the
-  // 8-GPU shape, a round of 233 digits with 9 populated, ~0.7 ms of empty
-  // blocks)
-  std::vector<uint32_t> cseg(nseg, 0);
-  for (uint32_t s = 0; s < nseg; ++s) {
-    maxseg = std::max(maxseg, segsize[s]);
-    cseg[s] = npop;
-    if (segsize[s]) segsize[npop++] = segsize[s];
-  }
-  segsize.resize(npop);
-  nseg = npop;
-  // digit passes: the fewest that bring the largest segment's mean bucket
-  // (its keys / RADIX^d, values uniform within a segment) to <= 8320 keys
-  // (the 512 x 17-key block holds that + 3.5 sigma), within `bits`
-  const int hyb = hybrid_mode_for(st);
-  int depths = 0;
-  if (bits > 0 && (hyb == 2 ? n >= 1024 : (hyb == 1 && n >= kPiecesMinKeys))) {
-    for (int d = 1; d * digit_bits <= bits; ++d) {
-      depths = d;
-      if ((double)maxseg / std::ldexp(1.0, d * digit_bits) <= 8320.0) break;
-    }
-    if (((uint64_t)nseg << (digit_bits * depths)) > (1ull << 22)) depths = 0;
-  }
-  // host table (pinned staging, one upload): pieces uint4 (off, len, seg,
-  // first tile) | ctile0[nseg + 1] | cstart[nseg] | cum[K + 1] (keys before
-  // each piece) | (8-byte aligned) the gather table of the fallback:
-  // src_off[K] | dst_off[K] | len[K] (uint64)
-  // (24-bit pieces: a 4th gather column, each piece's top byte << 24, and
-  // after it seghi[nseg] (u32) for the reserved depth 0's loader)
+  // host table (hybrid_plan.h piece_table; pinned staging, one upload)
   const uint32_t TILE = (uint32_t)(tp_block<uint32_t>(digit_bits) * tp_items<uint32_t>(digit_bits));
-  const size_t w32 = 4 * (size_t)K + 2 * (size_t)nseg + 1 + (size_t)K + 1;
-  const size_t g64 = (w32 + 1) / 2;  // first uint64 word of the gather table
-  const size_t gcols = planar ? 4 : 3;
-  const size_t words = g64 + gcols * (size_t)K + (planar ? ((size_t)nseg + 1) / 2 : 0);
-  LS_TRY(ws.ensure_seg(words));
-  LS_TRY(hipEventSynchronize(ws.seg_evt));  // the staging may still feed the previous upload
-  uint32_t* h32 = reinterpret_cast<uint32_t*>(ws.seg_host);
-  uint64_t* hg = ws.seg_host + g64;
-  uint32_t* ct0 = h32 + 4 * (size_t)K;
-  uint32_t* cst = ct0 + nseg + 1;
-  uint32_t* pcum = cst + nseg;
-  {
-    uint64_t run = 0;
-    for (uint32_t s = 0; s < nseg; ++s) {
-      cst[s] = (uint32_t)run;
-      run += segsize[s];
-    }
-  }
-  uint32_t tile = 0, i = 0, run = 0;
-  std::vector<uint64_t> dpos(cst, cst + nseg);
-  for (uint32_t s = 0; s <= nseg; ++s) {
-    ct0[s] = tile;  // segment s's pieces start at this tile
-    for (; i < K && (s == nseg || cseg[seg[keep[i]]] == s); ++i) {
-      const size_t p = keep[i];
-      const uint32_t cs = cseg[seg[p]];
-      pcum[i] = run;
-      run += (uint32_t)len[p];
-      h32[4 * (size_t)i + 0] = (uint32_t)off[p];
-      h32[4 * (size_t)i + 1] = (uint32_t)len[p];
-      h32[4 * (size_t)i + 2] = cs;
-      h32[4 * (size_t)i + 3] = tile;
-      tile += (uint32_t)((len[p] + TILE - 1) / TILE);
-      hg[i] = off[p];
-      hg[K + i] = dpos[cs];
-      hg[2 * (size_t)K + i] = len[p];
-      if (planar) hg[3 * (size_t)K + i] = (uint64_t)(pl.hi0 + seg[p]) << 24;
-      dpos[cs] += len[p];
-    }
-  }
-  pcum[K] = run;
-  uint32_t* shi = reinterpret_cast<uint32_t*>(hg + gcols * (size_t)K);
-  if (planar)
-    for (uint32_t i2 = 0; i2 < K; ++i2) shi[cseg[seg[keep[i2]]]] = (pl.hi0 + seg[keep[i2]]) << 24;
-  LS_TRY(hipMemcpyAsync(ws.seg_dev, ws.seg_host, words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  hipError_t staging = hipSuccess;
+  const PieceTable pt = piece_table(
+      off, len, seg, np, nseg, n, bits, digit_bits, hybrid_serves(hybrid_mode_for(st), n, kPiecesMinKeys, 0xffffffffull),
+      TILE, planar, pl.hi0, [&](size_t words) -> uint64_t* {
+        staging = ws.ensure_seg(words);
+        // the staging may still feed the previous upload
+        if (staging == hipSuccess) staging = hipEventSynchronize(ws.seg_evt);
+        return staging == hipSuccess ? ws.seg_host : nullptr;
+      });
+  if (!pt.ok) return hipErrorInvalidValue;
+  LS_TRY(staging);
+  LS_TRY(hipMemcpyAsync(ws.seg_dev, ws.seg_host, pt.words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   // seg_evt guards the staging against the next call; a sort the hybrid
   // handled has already waited for a kernel behind this copy (the bucket
   // stats' sequence word), so only the other paths record it (an event
   // costs the stream ~6 us)
-  if (depths > 0) {
+  if (pt.depths > 0) {
     const uint32_t* dev32 = reinterpret_cast<const uint32_t*>(ws.seg_dev);
-    HybPieces pc{dev32, K, nseg, tile, depths, (double)npop / nseg, dev32 + (pcum - h32)};
+    HybPieces pc{dev32, pt.K, pt.nseg, pt.tiles, pt.depths, pt.fill, dev32 + pt.cum};
     if (planar) {
       pc.i16 = pl.i16;
       pc.i8 = pl.i8;
-      pc.seghi = reinterpret_cast<const uint32_t*>(ws.seg_dev + g64 + gcols * (size_t)K);
+      pc.seghi = reinterpret_cast<const uint32_t*>(ws.seg_dev + pt.seghi64);
     }
     bool handled = false;
-    NoValue* nv = nullptr;
-    hipError_t e;
-    if (bias && digit_bits == 4)
-      e = sort_hybrid<4, BiasedDigit>(ws, in, out, tmp, nv, nv, nv, n, bits, bias, st, &handled, 0, &pc);
-    else if (bias)
-      e = sort_hybrid<8, BiasedDigit>(ws, in, out, tmp, nv, nv, nv, n, bits, bias, st, &handled, 0, &pc);
-    else if (digit_bits == 4)
-      e = sort_hybrid<4, RadixDigit>(ws, in, out, tmp, nv, nv, nv, n, bits, 0u, st, &handled, 0, &pc);
-    else
-      e = sort_hybrid<8, RadixDigit>(ws, in, out, tmp, nv, nv, nv, n, bits, 0u, st, &handled, 0, &pc);
+    const hipError_t e = sort_hybrid_u32(ws, in, out, tmp, n, bits, digit_bits, bias, st, &handled, 0, &pc);
     if (e != hipSuccess) {
       // a failure may come before the sequence-word wait: guard the staging
       // with the event after all, so the next call's
@@ -5453,35 +5184,31 @@ hipError_t sort_pieces_impl(Workspace& ws, const uint32_t* in, const PlanarPiece
       (void)hipEventRecord(ws.seg_evt, st);
       return e;
     }
-    if (handled) {
-      ws.last_algo = 4;
-      return hipSuccess;
-    }
+    if (handled) return hipSuccess;
   }
   LS_TRY(hipEventRecord(ws.seg_evt, st));
   // small or skewed: gather the pieces into segment order, LSD sort in place
   // (bits == 0: the segments are single values, already in order); 24-bit
   // pieces are unpacked by the gather
   if (planar) {
-    if (K > 65535) return hipErrorInvalidValue;
     {
       ScopedTimer tm("segcopy", st, n);
-      hipLaunchKernelGGL(k_segment_copy2d_planar, dim3((uint32_t)((maxlen + kSegPiece - 1) / kSegPiece), K),
-                         dim3(256), 0, st, pl.i16, pl.i8, out, ws.seg_dev + g64, K);
+      hipLaunchKernelGGL(k_segment_copy2d_planar, dim3((uint32_t)((pt.maxlen + kSegPiece - 1) / kSegPiece), pt.K),
+                         dim3(256), 0, st, pl.i16, pl.i8, out, ws.seg_dev + pt.g64, pt.K);
       LS_TRY(hipGetLastError());
     }
     // the unpacked keys lie in [top byte of the first populated segment,
     // that of the last + 1) << 24: a range sort of that span (the range
     // hybrid for large rounds) instead of a 32-bit LSD sort -- the rounds of
     // more than 32 segments or without the reserved depth 0
-    const uint32_t s0 = seg[keep[0]], s1 = seg[keep[K - 1]];
+    const uint32_t s0 = pt.first_seg, s1 = pt.last_seg;
     const uint32_t lo_key = (pl.hi0 + s0) << 24;
     const uint64_t span = (uint64_t)(s1 - s0 + 1) << 24;
     int W = 24;
     while (((uint64_t)1 << W) < span) ++W;
     return sort_u32(ws, out, out, tmp, n, 0, W, digit_bits, nullptr, st, lo_key, true, span);
   } else {
-    LS_TRY(segment_copy_dev_u32(in, out, ws.seg_dev + g64, K, maxlen, n, st));
+    LS_TRY(segment_copy_dev_u32(in, out, ws.seg_dev + pt.g64, pt.K, pt.maxlen, n, st));
   }
   if (bits == 0) return hipSuccess;
   return sort_impl<uint32_t, NoValue>(ws, out, out, tmp, nullptr, nullptr, nullptr, n, 0, 32, digit_bits, st);
@@ -5508,19 +5235,11 @@ hipError_t sort_pairs_u32_u32(Workspace& ws, const uint32_t* kin, const uint32_t
   // full-width sorts: the MSD hybrid (stable; the payloads travel with the keys)
   const int hyb = hybrid_mode_for(st);
   if (lo == 0 && hi == 32 && (digit_bits == 8 || digit_bits == 4) &&
-      ((hyb == 1 && n >= kHybMinKeys && n <= kHybMaxKeysPairs) || (hyb == 2 && n >= 1024 && n <= kHybMaxKeysPairs)) &&
+      hybrid_serves(hyb, n, kHybMinKeys, kHybMaxKeysPairs) &&
       (get_algorithm() == 0 || get_algorithm() == 3) && kin != ktmp) {
     bool handled = false;
-    if (digit_bits == 8)
-      LS_TRY((sort_hybrid<8, RadixDigit, uint32_t, uint32_t>(ws, kin, kout, ktmp, vin, vout, vtmp, n, 32, 0u, st,
-                                                              &handled)));
-    else
-      LS_TRY((sort_hybrid<4, RadixDigit, uint32_t, uint32_t>(ws, kin, kout, ktmp, vin, vout, vtmp, n, 32, 0u, st,
-                                                              &handled)));
-    if (handled) {
-      ws.last_algo = 4;
-      return hipSuccess;
-    }
+    LS_TRY(sort_hybrid_bits<RadixDigit>(digit_bits, ws, kin, kout, ktmp, vin, vout, vtmp, n, 32, 0u, st, &handled));
+    if (handled) return hipSuccess;
   }
   return sort_impl<uint32_t, uint32_t>(ws, kin, kout, ktmp, vin, vout, vtmp, n, lo, hi, digit_bits, st);
 }
@@ -5534,17 +5253,11 @@ hipError_t sort_64_hybrid_or_lsd(Workspace& ws, const uint64_t* kin, uint64_t* k
                                  V* vout, V* vtmp, size_t n, int lo, int hi, int digit_bits, hipStream_t st) {
   const int hyb = hybrid_mode_for(st);
   if (lo == 0 && hi == 64 && (digit_bits == 8 || digit_bits == 4) &&
-      ((hyb == 1 && n >= kHybMinKeys64 && n <= kHybMaxKeys64) || (hyb == 2 && n >= 1024 && n <= kHybMaxKeys64)) &&
+      hybrid_serves(hyb, n, kHybMinKeys64, kHybMaxKeys64) &&
       (get_algorithm() == 0 || get_algorithm() == 3) && (const void*)kin != (const void*)ktmp) {
     bool handled = false;
-    if (digit_bits == 8)
-      LS_TRY((sort_hybrid<8, RadixDigit, uint64_t, V>(ws, kin, kout, ktmp, vin, vout, vtmp, n, 64, 0u, st, &handled)));
-    else
-      LS_TRY((sort_hybrid<4, RadixDigit, uint64_t, V>(ws, kin, kout, ktmp, vin, vout, vtmp, n, 64, 0u, st, &handled)));
-    if (handled) {
-      ws.last_algo = 4;
-      return hipSuccess;
-    }
+    LS_TRY(sort_hybrid_bits<RadixDigit>(digit_bits, ws, kin, kout, ktmp, vin, vout, vtmp, n, 64, 0u, st, &handled));
+    if (handled) return hipSuccess;
   }
   return sort_impl<uint64_t, V>(ws, kin, kout, ktmp, vin, vout, vtmp, n, lo, hi, digit_bits, st);
 }

@@ -13,7 +13,7 @@ import pytest
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
 
-@pytest.mark.parametrize("src", ["distrib_sim", "boundaries_test"])
+@pytest.mark.parametrize("src", ["distrib_sim", "boundaries_test", "hybrid_plan_test"])
 def test_host_arithmetic_asan(tmp_path, src):
     """distrib_sim: the multi-GPU schedules' host arithmetic over simulated
     ranks; boundaries_test: gpuPartial's reference-boundaries mode
